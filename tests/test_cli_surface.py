@@ -14,6 +14,15 @@ import pytest
 REPO = Path(__file__).resolve().parent.parent
 
 
+def _no_gpu_env():
+    """Child-process environment with every GPU hidden, so a test of the
+    CPU-only behaviour checks the same thing on a GPU box."""
+    import os
+
+    return dict(os.environ, HIP_VISIBLE_DEVICES="-1",
+                CUDA_VISIBLE_DEVICES="-1")
+
+
 def test_inference_cli_dir_show_split(tmp_path):
     """A directory source enhances every image; --show-split writes the
     before/after composite (white divider at w//2)."""
@@ -260,7 +269,7 @@ def test_quickstart_example_runs():
     train -> score -> enhance on synthetic data) completes on CPU."""
     out = subprocess.run(
         [sys.executable, str(REPO / "examples" / "quickstart.py")],
-        capture_output=True, text=True, timeout=600,
+        capture_output=True, text=True, timeout=600, env=_no_gpu_env(),
     )
     assert out.returncode == 0, out.stderr
     assert "enhanced frame: (64, 64, 3) uint8" in out.stdout
@@ -311,7 +320,7 @@ def test_engine_fast_on_cpu_clear_error():
         [sys.executable, str(REPO / "train.py"), "--engine", "fast",
          "--synthetic", "4", "--epochs", "1",
          "--batch-size", "2", "--height", "32", "--width", "32"],
-        capture_output=True, text=True, timeout=600,
+        capture_output=True, text=True, timeout=600, env=_no_gpu_env(),
     )
     assert out.returncode != 0
     assert "--engine fast requires a ROCm GPU" in out.stderr
@@ -320,7 +329,7 @@ def test_engine_fast_on_cpu_clear_error():
         [sys.executable, str(REPO / "score.py"), "--engine", "fast",
          "--weights", "w.pt", "--synthetic", "4",
          "--batch-size", "2", "--height", "32", "--width", "32"],
-        capture_output=True, text=True, timeout=600,
+        capture_output=True, text=True, timeout=600, env=_no_gpu_env(),
     )
     assert out.returncode != 0
     assert "requires a ROCm GPU" in out.stderr
