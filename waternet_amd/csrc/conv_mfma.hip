@@ -13,6 +13,10 @@
 //   - k_conv_wgrad<KS,BK,CH>: weight gradient as reduction GEMM over M,
 //     m-major LDS images + ds_read_b64_tr_b16 hardware transpose reads,
 //     fp32 atomic accumulation into the NCHW fp32 grad tensor.
+//   - k_conv_wgrad_patch<KS,BK,CT,CH>: weight gradient for KS >= 3 and
+//     32/64-multiple channel classes: one X row segment staged once, the
+//     KS dx taps taken by row-shifted tr reads, LDS-transposed epilogue so
+//     the atomics are contiguous.
 //   - k_wgrad_smallk: VALU outer-product path for K <= 4 output convs.
 //   - k_bias_grad(+_reduce): slab-partial column sums of dY.
 //   - k_pack_fwd / k_pack_dgrad / k_pack_all: NCHW fp32 masters -> bf16
@@ -984,6 +988,307 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad(
 }
 
 // ---------------------------------------------------------------------------
+// Patch weight gradient: stage each X row segment ONCE and take the KS dx
+// taps by shifted tr reads.
+//
+// k_conv_wgrad stages X once per tap (RS x the unique bytes) because its
+// [col/16][m/4][4m][16col] image only admits 4m-aligned shifts. Here both
+// operands are plain [pixel][channel] rows: ds_read_b64_tr_b16 takes a
+// per-lane address of 4 contiguous elements of one row, so the fragment of
+// tap dx is the dx=0 read with every lane moved by dx whole pixel rows —
+// always 8-byte aligned.
+//
+//   - a block owns one BK k-tile, one CT channel tile, ONE dy tap row and a
+//     contiguous slice of m-chunks; it accumulates all KS dx taps (KS
+//     32x32 accumulator tiles per wave).
+//   - an m-chunk is CH consecutive output pixels of one image row, so
+//     (n, oy, ox0) is block-uniform: no per-lane division. Rows whose input
+//     row oy+dy-PAD falls outside the image contribute nothing and are not
+//     enumerated at all.
+//   - per chunk: dY [CH][BK] once, the X patch [CH+KS-1][CT] of input row
+//     oy+dy-PAD once (halo from global memory; lanes outside the image or
+//     past the row end source the 16 B zero buffer).
+//   - images: 64 B rows (32 channels) need no swizzle: 4 consecutive pixels
+//     cover the 64 banks exactly. 128 B rows (64 channels) XOR byte-bit 6
+//     with pixel-bit 1, so ANY 4 consecutive pixels (every dx shift) hit 4
+//     distinct 64 B bank quarters. The XOR moves whole 16 B chunks, so the
+//     glds image stays lane-linear with the swizzle on the SOURCE chunk.
+//   - 4 waves = WR x WC 32x32 output quadrants x WK k-step interleave
+//     (BK=CT=64: 2x2x1; BK=CT=32: 1x1x4, each wave every 4th k-step).
+//   - per k-step: 2 A tr reads shared by all KS taps + 2*KS B tr reads,
+//     KS v_mfma_f32_32x32x16_bf16, 2-deep ring with counted lgkmcnt.
+// ---------------------------------------------------------------------------
+
+// byte offset of (pixel row, column) inside a [pixel][COLS] bf16 image
+constexpr int pt_swz(int pix, int COLS) {
+  return COLS == 64 ? ((pix >> 1) & 1) << 6 : 0;
+}
+constexpr int pt_off(int pix, int col, int COLS) {
+  return pix * COLS * 2 + ((col * 2) ^ pt_swz(pix, COLS));
+}
+// glds staging slot -> image pixel row / SOURCE 16 B channel chunk
+constexpr int pt_slot_pix(int slot, int COLS) { return slot / (COLS / 8); }
+constexpr int pt_slot_chunk(int slot, int COLS) {
+  return (slot % (COLS / 8)) ^ (pt_swz(pt_slot_pix(slot, COLS), COLS) >> 4);
+}
+// the slot map lands slot s at byte 16*s and covers every chunk of every
+// pixel row exactly once (lane-linear glds image)
+constexpr bool pt_image_linear(int NPIX, int COLS) {
+  const int CPR = COLS / 8;
+  for (int pix = 0; pix < NPIX; ++pix) {
+    unsigned seen = 0;
+    for (int c = 0; c < CPR; ++c) {
+      const int s = pix * CPR + c;
+      if (pt_slot_pix(s, COLS) != pix) return false;
+      const int ch = pt_slot_chunk(s, COLS);
+      if (ch < 0 || ch >= CPR) return false;
+      if (pt_off(pix, ch * 8, COLS) != 16 * s) return false;
+      seen |= 1u << ch;
+    }
+    if (seen != (1u << CPR) - 1) return false;
+  }
+  return true;
+}
+// the 32x32x16 transposed read (per 32-lane half: 2 column blocks x 4
+// pixel rows x 4 8-byte pieces) is bank-conflict-free at every pixel shift
+constexpr bool pt_tr_conflict_free(int COLS, int maxShift) {
+  for (int sh = 0; sh <= maxShift; ++sh)
+    for (int c32 = 0; c32 < COLS / 32; ++c32) {
+      unsigned long long used = 0;
+      for (int l = 0; l < 32; ++l) {
+        const int pix = sh + ((l & 15) >> 2);
+        const int col = c32 * 32 + ((l >> 4) & 1) * 16 + (l & 3) * 4;
+        const int a = pt_off(pix, col, COLS);
+        if (a % 8 != 0) return false;
+        const unsigned long long bits = 3ull << ((a / 4) % 64);
+        if (used & bits) return false;
+        used |= bits;
+      }
+    }
+  return true;
+}
+
+template <int KS, int BK, int CT, int CH>
+__global__ __launch_bounds__(256, 2) void k_conv_wgrad_patch(
+    const bf16_t* __restrict__ dY,  // (N,H,W,Kp)
+    const bf16_t* __restrict__ X,   // (N,H,W,Cp)
+    float* __restrict__ dW,         // (K, C, KS, KS) fp32, accumulated into
+    int N, int H, int W, int Cp, int Kp, int K, int C, int nSeg,
+    const bf16_t* __restrict__ Zero16w) {
+  static_assert(WN_MFMA_KMAP == 0, "wgrad staging assumes KMAP 0");
+  static_assert((BK == 32 || BK == 64) && (CT == 32 || CT == 64));
+  constexpr int PAD = KS / 2;
+  constexpr int WR = BK / 32, WC = CT / 32;  // wave grid over the tile
+  constexpr int WK = 4 / (WR * WC);          // waves interleaving k-steps
+  constexpr int KST = CH / 16;               // k-steps per chunk
+  static_assert(CH % 16 == 0 && KST % WK == 0);
+  constexpr int KSTW = KST / WK;             // k-steps per wave
+  constexpr int NPX = CH + KS - 1;           // patch pixels (2*PAD halo)
+  constexpr int ACPR = BK / 8, BCPR = CT / 8;  // 16 B chunks per row
+  constexpr int ASLOTS = CH * ACPR, BSLOTS = NPX * BCPR;
+  constexpr int SA = (ASLOTS + 255) / 256, SB = (BSLOTS + 255) / 256;
+  constexpr int ABYTES = SA * 256 * 16;  // padded: surplus slots stay inside
+  constexpr int BBYTES = SB * 256 * 16;
+  static_assert(pt_image_linear(CH, BK) && pt_image_linear(NPX, CT),
+                "glds slot order != image chunk order");
+  static_assert(pt_tr_conflict_free(BK, 12) &&
+                    pt_tr_conflict_free(CT, KS - 1 + 12),
+                "tr read bank conflict");
+  // last pixel row a tr read touches: last k-step, upper lane half, second
+  // 4-pixel read, row 3 (+ the last dx for the patch); the swizzle stays
+  // inside a row, so the row end bounds every lane address
+  static_assert((CH - 16 + 8 + 4 + 3 + 1) * BK * 2 <= ASLOTS * 16);
+  static_assert((CH - 16 + 8 + 4 + 3 + (KS - 1) + 1) * CT * 2 <= BSLOTS * 16);
+
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* lA = smem;               // 2 x ABYTES
+  char* lB = smem + 2 * ABYTES;  // 2 x BBYTES
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int wk = wid / (WR * WC);
+  const int wr = (wid % (WR * WC)) / WC;
+  const int wc = wid % WC;
+  const int kt0 = blockIdx.x * BK;
+  const int ct0 = (blockIdx.y / KS) * CT;
+  const int dy_ = blockIdx.y % KS;
+
+  // output rows whose input row oy + dy - PAD lies inside the image
+  const int oyLo = max(0, PAD - dy_);
+  const int Hv = min(H, H + PAD - dy_) - oyLo;
+  if (Hv <= 0) return;  // block-uniform, nothing staged or read yet
+  const int total = N * Hv * nSeg;
+  const int per = (total + (int)gridDim.z - 1) / (int)gridDim.z;
+  const int c0 = blockIdx.z * per;
+  const int c1 = min(total, c0 + per);
+  if (c0 >= c1) return;  // block-uniform
+  int n = c0 / (Hv * nSeg);
+  int oyv = (c0 - n * Hv * nSeg) / nSeg;
+  int seg = c0 - (n * Hv + oyv) * nSeg;
+
+  // ---- static slot geometry (slot -> pixel row, source chunk) ----
+  int aPix[SA], aCh[SA], bPix[SB], bCh[SB];
+#pragma unroll
+  for (int s = 0; s < SA; ++s) {
+    const int sg = tid + s * 256;
+    aPix[s] = (sg < ASLOTS) ? pt_slot_pix(sg, BK) : (1 << 28);  // -> zero
+    aCh[s] = pt_slot_chunk(sg, BK) * 8;
+  }
+#pragma unroll
+  for (int s = 0; s < SB; ++s) {
+    const int sg = tid + s * 256;
+    bPix[s] = (sg < BSLOTS) ? pt_slot_pix(sg, CT) - PAD : (1 << 28);
+    bCh[s] = pt_slot_chunk(sg, CT) * 8;
+  }
+
+  auto stage = [&](int buf, int n_, int oy, int sg_) {
+    const int ox0 = sg_ * CH;
+    const long rowm = ((long)n_ * H + oy) * W;
+    const long rowx = ((long)n_ * H + oy + dy_ - PAD) * W;
+#pragma unroll
+    for (int s = 0; s < SA; ++s) {
+      const bf16_t* src = Zero16w;
+      const int ox = ox0 + aPix[s];
+      if (ox < W) src = dY + (rowm + ox) * Kp + kt0 + aCh[s];
+      __builtin_amdgcn_global_load_lds(
+          src, lA + buf * ABYTES + (tid + s * 256) * 16, 16, 0, 0);
+    }
+#pragma unroll
+    for (int s = 0; s < SB; ++s) {
+      const bf16_t* src = Zero16w;
+      const int ix = ox0 + bPix[s];
+      if (ix >= 0 && ix < W) src = X + (rowx + ix) * Cp + ct0 + bCh[s];
+      __builtin_amdgcn_global_load_lds(
+          src, lB + buf * BBYTES + (tid + s * 256) * 16, 16, 0, 0);
+    }
+  };
+
+  f32x16 acc[KS];
+#pragma unroll
+  for (int t = 0; t < KS; ++t)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
+
+  // per-lane tr-read bases. Lane l reads column (l&31) of its 32-wide
+  // block: 16-column half (l>>4)&1, reduction pixels (l>>5)*8 + 4h + e;
+  // inside the 16-lane group, lane 4q+p addresses row q, columns 4p..4p+3.
+  // The pixel of a read is rowl + (16*kst + 4h + dx): only (q + dx) & 2
+  // feeds the swizzle, so 4 B bases (dx & 3) cover every shift.
+  const int q = (lane & 15) >> 2;
+  const int rowl = wk * 16 + (lane >> 5) * 8 + q;
+  const int acol2 = (wr * 32 + ((lane >> 4) & 1) * 16 + (lane & 3) * 4) * 2;
+  const int bcol2 = (wc * 32 + ((lane >> 4) & 1) * 16 + (lane & 3) * 4) * 2;
+  const unsigned aB0 = (unsigned)(unsigned long long)lA +
+                       (unsigned)(rowl * BK * 2 + (acol2 ^ pt_swz(q, BK)));
+  unsigned bB0[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+    bB0[c] = (unsigned)(unsigned long long)lB +
+             (unsigned)(rowl * CT * 2 + (bcol2 ^ pt_swz(q + c, CT)));
+
+  int buf = 0;
+  stage(0, n, oyLo + oyv, seg);
+  __syncthreads();  // drains the DMA (vmcnt 0) + barrier
+  for (int c = c0; c < c1; ++c) {
+    if (++seg == nSeg) {
+      seg = 0;
+      if (++oyv == Hv) { oyv = 0; ++n; }
+    }
+    if (c + 1 < c1) stage(buf ^ 1, n, oyLo + oyv, seg);  // DMA under the math
+    const unsigned aB = aB0 + (unsigned)(buf * ABYTES);
+    unsigned bB[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) bB[i] = bB0[i] + (unsigned)(buf * BBYTES);
+
+    constexpr int RPK = 2 + 2 * KS;  // tr reads per k-step
+    bf16x4 aT[2][2], bT[2][KS][2];   // 2-deep k-step ring
+    auto rdk = [&](int i, int ring) {
+      const int p0 = i * WK * 16;  // first pixel of this wave's i-th k-step
+      aT[ring][0] = ds_tr16(aB + (unsigned)(p0 * BK * 2));
+      aT[ring][1] = ds_tr16(aB + (unsigned)((p0 + 4) * BK * 2));
+#pragma unroll
+      for (int dx = 0; dx < KS; ++dx) {
+        bT[ring][dx][0] =
+            ds_tr16(bB[dx & 3] + (unsigned)((p0 + dx) * CT * 2));
+        bT[ring][dx][1] =
+            ds_tr16(bB[dx & 3] + (unsigned)((p0 + 4 + dx) * CT * 2));
+      }
+    };
+    rdk(0, 0);
+#pragma unroll
+    for (int i = 0; i < KSTW; ++i) {
+      const int ring = i & 1;
+      if (i + 1 < KSTW) {
+        rdk(i + 1, ring ^ 1);
+        // wait for THIS k-step's reads only (lgkmcnt saturates at 15, so
+        // KS=7's 16 in-flight reads wait for one more than needed)
+        if constexpr (RPK == 8)
+          asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
+        else if constexpr (RPK == 12)
+          asm volatile("s_waitcnt lgkmcnt(12)" ::: "memory");
+        else
+          asm volatile("s_waitcnt lgkmcnt(15)" ::: "memory");
+      } else {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      const bf16x8 av = __builtin_shufflevector(
+          aT[ring][0], aT[ring][1], 0, 1, 2, 3, 4, 5, 6, 7);
+#pragma unroll
+      for (int dx = 0; dx < KS; ++dx) {
+        const bf16x8 bv = __builtin_shufflevector(
+            bT[ring][dx][0], bT[ring][dx][1], 0, 1, 2, 3, 4, 5, 6, 7);
+        acc[dx] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc[dx],
+                                                          0, 0, 0);
+      }
+    }
+    if (c + 1 < c1) __syncthreads();  // drains DMA + joins waves
+    buf ^= 1;
+  }
+
+  // ---- epilogue: D col = lane&31 (c), row = (r&3) + 8*(r>>2) +
+  //      4*(lane>>5) (k). The kernel is bound by the fp32 atomics, not the
+  //      math: straight from the D layout every lane of an atomic hits its
+  //      own cache line (c stride = KS*KS floats). So the tile goes through
+  //      LDS in 4 slabs of WR*8 k rows laid out [k][c][dx] — dW's own order
+  //      for one dy — the WK k-step waves' partial sums are added on the
+  //      way out, and consecutive lanes add to consecutive addresses. ----
+  constexpr int SLABN = WR * 8 * CT * KS;  // floats per slab copy
+  // all WK slab copies: 4096*KS bytes; the host sizes LDS to the larger of
+  // this and the staging buffers
+  static_assert(WK * SLABN * 4 == 4096 * KS);
+  float* slab = reinterpret_cast<float*>(smem);
+  __syncthreads();  // every wave is past its last tr read; no DMA in flight
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      const int kk = wr * 8 + rr + 4 * (lane >> 5);
+      float* dst =
+          slab + wk * SLABN + (kk * CT + wc * 32 + (lane & 31)) * KS;
+#pragma unroll
+      for (int dx = 0; dx < KS; ++dx) dst[dx] = acc[dx][4 * j + rr];
+    }
+    __syncthreads();
+    for (int e = tid; e < SLABN; e += 256) {
+      float v = slab[e];
+#pragma unroll
+      for (int w = 1; w < WK; ++w) v += slab[w * SLABN + e];
+      const int kk = e / (CT * KS);
+      const int rem = e - kk * (CT * KS);
+      const int cc = rem / KS;
+      const int dx = rem - cc * KS;
+      const int k = kt0 + (kk >> 3) * 32 + j * 8 + (kk & 7);
+      const int cch = ct0 + cc;
+      if (k < K && cch < C)
+        atomicAdd(&dW[(((long)k * C + cch) * KS + dy_) * KS + dx], v);
+    }
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Small-K weight gradient (K <= 4: the 64->3 / 32->3 output convs).
 // The MFMA path wastes 13/16 rows of every fragment on Kp padding there;
 // a VALU outer-product reduction is ~10x cheaper. Each block owns one
@@ -1439,6 +1744,80 @@ void launch_conv_bn(const at::Tensor& x, const at::Tensor& wp,
   HIP_CHECK_LAST();
 }
 
+// (KS, Cp, Kp) classes where k_conv_wgrad_patch measured faster than
+// k_conv_wgrad on MI355X (table: docs/KERNELS.md, wgrad section).
+inline bool wgrad_patch_wins(int ks, int Cp, int Kp) {
+  (void)ks; (void)Cp; (void)Kp;
+  return true;
+}
+
+template <int KS, int BKCT, int CH>
+void launch_wgrad_patch_t(const at::Tensor& dy, const at::Tensor& x,
+                          at::Tensor& dw, const bf16_t* zero16,
+                          hipStream_t stream) {
+  const int N = x.size(0), H = x.size(1), W = x.size(2), Cp = x.size(3);
+  const int Kp = dy.size(3);
+  const int K = dw.size(0), C = dw.size(1);
+  const int nSeg = (W + CH - 1) / CH;
+  const int gx = Kp / BKCT, gy = (Cp / BKCT) * KS;
+  // Split-m block count. The kernel's time is main loop + epilogue
+  // atomics: T(blocks) ~ a*work/blocks + b*blocks*tile, with work =
+  // gx*gy*chunks*k-steps and tile = BK*CT*KS atomics per block, so the
+  // optimum is blocks ~ sqrt(work/tile). The constant is fitted to block
+  // sweeps at 112^2 and 256^2 (docs/KERNELS.md); beyond ~3 resident blocks
+  // per CU more blocks only add atomics. WN_WGRAD_PATCH_BLOCKS overrides
+  // the count for A/B sweeps.
+  const double work = (double)gx * gy * N * H * nSeg * (CH / 16);
+  int blocks = (int)(110.0 * std::sqrt(work / (BKCT * BKCT * KS)));
+  blocks = std::min(blocks, 768);
+  if (const char* be = getenv("WN_WGRAD_PATCH_BLOCKS")) blocks = atoi(be);
+  int split = std::max(1, (blocks + gx * gy / 2) / (gx * gy));
+  split = (int)std::min<long>(split, (long)N * H * nSeg);
+  constexpr int SA = (CH * (BKCT / 8) + 255) / 256;
+  constexpr int SB = ((CH + KS - 1) * (BKCT / 8) + 255) / 256;
+  // staging double buffer, reused by the epilogue's 4096*KS-byte slab
+  const size_t lds =
+      std::max<size_t>((size_t)2 * (SA + SB) * 256 * 16, (size_t)4096 * KS);
+  hipLaunchKernelGGL((k_conv_wgrad_patch<KS, BKCT, BKCT, CH>),
+                     dim3(gx, gy, split), dim3(256), lds, stream,
+                     (const bf16_t*)dy.data_ptr(),
+                     (const bf16_t*)x.data_ptr(), dw.data_ptr<float>(), N, H,
+                     W, Cp, Kp, K, C, nSeg, zero16);
+}
+
+void launch_wgrad_patch(const at::Tensor& dy, const at::Tensor& x,
+                        at::Tensor& dw, int ks, int cls,
+                        const bf16_t* zero16, hipStream_t stream) {
+  // chunk length: the instantiated CH that pads a row the least (112 = 7
+  // k-steps covers the flagship's 112-pixel rows exactly; 64 divides the
+  // 256/512 widths). WN_WGRAD_PATCH_CH overrides it for tests and A/B
+  // runs; it is read per call so one process can exercise both.
+  const char* fe = getenv("WN_WGRAD_PATCH_CH");
+  const int force_ch = fe ? atoi(fe) : 0;
+  const int W = x.size(2);
+  int ch = 64;
+  if (cls == 64) {
+    const int pad64 = (W + 63) / 64 * 64, pad112 = (W + 111) / 112 * 112;
+    ch = (pad112 < pad64) ? 112 : 64;
+    if (force_ch == 64 || force_ch == 112) ch = force_ch;
+  }
+  auto go = [&](auto ks_const) {
+    constexpr int KSV = decltype(ks_const)::value;
+    if (cls == 32)
+      launch_wgrad_patch_t<KSV, 32, 64>(dy, x, dw, zero16, stream);
+    else if (ch == 112)
+      launch_wgrad_patch_t<KSV, 64, 112>(dy, x, dw, zero16, stream);
+    else
+      launch_wgrad_patch_t<KSV, 64, 64>(dy, x, dw, zero16, stream);
+  };
+  switch (ks) {
+    case 3: go(std::integral_constant<int, 3>{}); break;
+    case 5: go(std::integral_constant<int, 5>{}); break;
+    case 7: go(std::integral_constant<int, 7>{}); break;
+    default: TORCH_CHECK(false, "unsupported kernel size ", ks);
+  }
+}
+
 }  // namespace
 
 at::Tensor conv2d_fwd(const at::Tensor& x, const at::Tensor& wp,
@@ -1495,6 +1874,28 @@ void conv2d_wgrad(const at::Tensor& dy, const at::Tensor& x, at::Tensor& dw,
                        MagicDiv::make((unsigned)W).mul);
     HIP_CHECK_LAST();
     return;
+  }
+  // Patch kernel (one X row segment staged once for all KS dx taps) for the
+  // channel classes it is instantiated for. WN_WGRAD_PATCH=0 forces the old
+  // kernel everywhere, =1 the patch kernel wherever it is supported; unset,
+  // each (KS, Cp, Kp) class takes whichever measured faster.
+  static const int patch_mode = [] {
+    const char* e = getenv("WN_WGRAD_PATCH");
+    return e == nullptr ? -1 : (atoi(e) != 0 ? 1 : 0);
+  }();
+  if (patch_mode != 0 && ks >= 3) {
+    const int cls = (Cp % 64 == 0 && Kp % 64 == 0) ? 64
+                    : (Cp == 32 && Kp == 32)       ? 32
+                                                   : 0;
+    if (cls != 0 && (patch_mode > 0 || wgrad_patch_wins((int)ks, Cp, Kp))) {
+      static thread_local at::Tensor zero16p;
+      if (!zero16p.defined() || zero16p.device() != x.device())
+        zero16p = at::zeros({8}, x.options());
+      launch_wgrad_patch(dy, x, dw, (int)ks, cls,
+                         (const bf16_t*)zero16p.data_ptr(), stream0);
+      HIP_CHECK_LAST();
+      return;
+    }
   }
   const int KG = (int)(ks * ks) * Cp;
   const int BK = std::min(Kp, 128);
