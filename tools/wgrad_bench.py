@@ -32,11 +32,16 @@ SHAPES = [  # (ks, C, K, label)
     (3, 64, 64, "cmg.conv7"),
     (7, 6, 32, "refiner.conv1(x3)"),
     (5, 32, 32, "refiner.conv2(x3)"),
+    # K <= 4: k_wgrad_smallk on both sides (WN_WGRAD_PATCH does not apply)
+    (3, 64, 3, "cmg.conv8"),
+    (3, 32, 3, "refiner.conv3(x3)"),
     # instantiated patch-kernel classes no WaterNet layer uses (not in TOTAL)
     (7, 128, 128, "extra k7 128"),
     (5, 64, 128, "extra k5 64-128"),
     (3, 32, 32, "extra k3 32"),
     (7, 32, 32, "extra k7 32"),
+    (5, 12, 64, "extra k5 16-64"),
+    (3, 12, 128, "extra k3 16-128"),
 ]
 
 
@@ -56,11 +61,13 @@ def patch_class(ks, Cp, Kp):
         return 64
     if Cp == 32 and Kp == 32:
         return 32
+    if Cp == 16 and (Kp == 32 or Kp % 64 == 0):
+        return 16  # k_conv_wgrad_patch16 (tap pairs)
     return 0
 
 
 def patch_chunk(cls, W):
-    if cls != 64:
+    if cls not in (64, 16):
         return 64
     forced = int(os.environ.get("WN_WGRAD_PATCH_CH", "0"))
     if forced in (64, 112):
@@ -72,6 +79,8 @@ def patch_chunk(cls, W):
 def staged_bytes(ks, Cp, Kp, N, H, W, patch):
     """Bytes one launch moves global->LDS (every glds slot, pads included)."""
     cls = patch_class(ks, Cp, Kp) if patch else 0
+    if Kp == 16:  # k_wgrad_smallk reads global memory directly
+        return 0
     if cls == 0:  # k_conv_wgrad: 64-row chunks, BK x 128 tiles
         BK = min(Kp, 128)
         cpk = (64 // 4 * 72 + 16) // 8
@@ -82,10 +91,16 @@ def staged_bytes(ks, Cp, Kp, N, H, W, patch):
         return chunks * (sa + sb) * 4096 * gx * gy
     CH = patch_chunk(cls, W)
     nseg = -(-W // CH)
-    sa = -(-CH * (cls // 8) // 256)
-    sb = -(-(CH + ks - 1) * (cls // 8) // 256)
     pad = ks // 2
     rows = sum(N * max(0, H - abs(d - pad)) for d in range(ks))
+    if cls == 16:  # Patch16Geo: BK 32/64, images padded to whole k-steps
+        BK = 32 if Kp == 32 else 64
+        pxa = -(-CH // 16 // (128 // BK)) * (128 // BK) * 16
+        sa = -(-pxa * (BK // 8) // 256)
+        sb = -(-(pxa + ks) * 2 // 256)
+        return rows * nseg * (sa + sb) * 4096 * (Kp // BK)
+    sa = -(-CH * (cls // 8) // 256)
+    sb = -(-(CH + ks - 1) * (cls // 8) // 256)
     return rows * nseg * (sa + sb) * 4096 * (Kp // cls) * (Cp // cls)
 
 

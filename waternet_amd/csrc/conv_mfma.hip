@@ -1289,6 +1289,264 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_patch(
 }
 
 // ---------------------------------------------------------------------------
+// Patch weight gradient for Cp = 16 (the 12->128 / 6->32 input convs): two
+// taps per MFMA.
+//
+// A 32-column fragment of a 16-channel image would be half padding. But a
+// pixel row of the [pixel][16] patch is 32 bytes, so two neighbouring pixels
+// are 32 contiguous channels: the transposed read at pixel shift dx with row
+// stride 16 elements delivers pixel p+dx in its low 16 columns and pixel
+// p+dx+1 in its high 16 — tap dx and tap dx+1 of the same 16 channels. One
+// 32x32x16 MFMA therefore accumulates D column c' = tap dx + (c' >> 4),
+// channel c' & 15, and shifts 0, 2, .. cover KS taps in (KS+1)/2
+// accumulators. For odd KS the high half of the last one is a phantom tap
+// dx = KS: the patch is one pixel longer (NPX = CH + KS) so its reads stay
+// inside the staged image, and the epilogue drops it.
+//
+// Ownership, chunking, staging and the slab epilogue are those of
+// k_conv_wgrad_patch with a single channel tile. 4 waves = WR 32-row k
+// quadrants x WK k-step interleave (BK=64: 2x2, BK=32: 1x4). CH/16 need not
+// divide by WK: the images are staged PXA >= CH pixel rows long, the surplus
+// rows of dY sourced from the zero buffer, so a padded k-step adds 0.
+// ---------------------------------------------------------------------------
+
+// the pair read: inside a 32-lane half the upper 16 lanes read one pixel row
+// further than the lower 16, so lanes share addresses (pixels q+1..q+3).
+// Identical addresses are one access; distinct ones must not share a bank.
+constexpr bool pt_tr_pair_conflict_free(int maxShift) {
+  for (int sh = 0; sh <= maxShift; ++sh) {
+    int addr[32] = {};
+    for (int l = 0; l < 32; ++l) {
+      const int pix = sh + ((l & 15) >> 2) + ((l >> 4) & 1);
+      const int a = pt_off(pix, (l & 3) * 4, 16);
+      if (a % 8 != 0) return false;
+      for (int m = 0; m < l; ++m)
+        if (addr[m] != a && (addr[m] / 8) % 32 == (a / 8) % 32) return false;
+      addr[l] = a;
+    }
+  }
+  return true;
+}
+
+template <int KS, int BK, int CH>
+struct Patch16Geo {
+  static constexpr int NT = (KS + 1) / 2;  // tap-pair accumulators
+  static constexpr int WR = BK / 32, WK = 4 / WR;
+  static constexpr int KST = CH / 16;
+  static constexpr int KSTW = (KST + WK - 1) / WK;  // k-steps per wave
+  static constexpr int PXA = KSTW * WK * 16;  // pixel rows the waves walk
+  static constexpr int NPX = CH + KS;         // 2*PAD halo + phantom pixel
+  static constexpr int ACPR = BK / 8, BCPR = 2;  // 16 B chunks per row
+  static constexpr int ASLOTS = CH * ACPR, BSLOTS = NPX * BCPR;
+  static constexpr int SA = (PXA * ACPR + 255) / 256;
+  static constexpr int SB = ((PXA + KS) * BCPR + 255) / 256;
+  static constexpr int ABYTES = SA * 256 * 16, BBYTES = SB * 256 * 16;
+  static constexpr int SLABN = WR * 8 * 16 * KS;  // floats per slab copy
+  static constexpr int LDS =
+      2 * (ABYTES + BBYTES) > WK * SLABN * 4 ? 2 * (ABYTES + BBYTES)
+                                             : WK * SLABN * 4;
+};
+
+template <int KS, int BK, int CH>
+__global__ __launch_bounds__(256, 2) void k_conv_wgrad_patch16(
+    const bf16_t* __restrict__ dY,  // (N,H,W,Kp)
+    const bf16_t* __restrict__ X,   // (N,H,W,16)
+    float* __restrict__ dW,         // (K, C, KS, KS) fp32, accumulated into
+    int N, int H, int W, int Kp, int K, int C, int nSeg,
+    const bf16_t* __restrict__ Zero16w) {
+  static_assert(WN_MFMA_KMAP == 0, "wgrad staging assumes KMAP 0");
+  static_assert(BK == 32 || BK == 64);
+  static_assert(CH % 16 == 0);
+  using G = Patch16Geo<KS, BK, CH>;
+  constexpr int CT = 16;
+  constexpr int PAD = KS / 2;
+  constexpr int NT = G::NT, WR = G::WR, WK = G::WK, KSTW = G::KSTW;
+  constexpr int PXA = G::PXA, NPX = G::NPX;
+  constexpr int ASLOTS = G::ASLOTS, BSLOTS = G::BSLOTS;
+  constexpr int SA = G::SA, SB = G::SB;
+  constexpr int ABYTES = G::ABYTES, BBYTES = G::BBYTES;
+  static_assert(pt_image_linear(CH, BK) && pt_image_linear(NPX, CT),
+                "glds slot order != image chunk order");
+  static_assert(pt_tr_conflict_free(BK, 12) &&
+                    pt_tr_pair_conflict_free(KS - 1 + 12),
+                "tr read bank conflict");
+  // last pixel row a tr read of a real k-step touches: last k-step, upper
+  // lane half, second 4-pixel read, row 3 (+ the last shift and the pair's
+  // second pixel for the patch) — inside the staged, defined image
+  static_assert((CH - 16 + 8 + 4 + 3 + 1) * BK * 2 <= ASLOTS * 16);
+  static_assert((CH - 16 + 8 + 4 + 3 + (KS - 1) + 1 + 1) * CT * 2 <=
+                BSLOTS * 16);
+  // the same for the padded k-steps: inside the zero-sourced surplus slots
+  static_assert(PXA * BK * 2 <= ABYTES && (PXA + KS) * CT * 2 <= BBYTES);
+
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* lA = smem;               // 2 x ABYTES
+  char* lB = smem + 2 * ABYTES;  // 2 x BBYTES
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int wk = wid / WR;
+  const int wr = wid % WR;
+  const int kt0 = blockIdx.x * BK;
+  const int dy_ = blockIdx.y;
+
+  // output rows whose input row oy + dy - PAD lies inside the image
+  const int oyLo = max(0, PAD - dy_);
+  const int Hv = min(H, H + PAD - dy_) - oyLo;
+  if (Hv <= 0) return;  // block-uniform, nothing staged or read yet
+  const int total = N * Hv * nSeg;
+  const int per = (total + (int)gridDim.z - 1) / (int)gridDim.z;
+  const int c0 = blockIdx.z * per;
+  const int c1 = min(total, c0 + per);
+  if (c0 >= c1) return;  // block-uniform
+  int n = c0 / (Hv * nSeg);
+  int oyv = (c0 - n * Hv * nSeg) / nSeg;
+  int seg = c0 - (n * Hv + oyv) * nSeg;
+
+  // ---- static slot geometry (slot -> pixel row, source chunk) ----
+  int aPix[SA], aCh[SA], bPix[SB], bCh[SB];
+#pragma unroll
+  for (int s = 0; s < SA; ++s) {
+    const int sg = tid + s * 256;
+    aPix[s] = (sg < ASLOTS) ? pt_slot_pix(sg, BK) : (1 << 28);  // -> zero
+    aCh[s] = pt_slot_chunk(sg, BK) * 8;
+  }
+#pragma unroll
+  for (int s = 0; s < SB; ++s) {
+    const int sg = tid + s * 256;
+    bPix[s] = (sg < BSLOTS) ? pt_slot_pix(sg, CT) - PAD : (1 << 28);
+    bCh[s] = pt_slot_chunk(sg, CT) * 8;
+  }
+
+  auto stage = [&](int buf, int n_, int oy, int sg_) {
+    const int ox0 = sg_ * CH;
+    const long rowm = ((long)n_ * H + oy) * W;
+    const long rowx = ((long)n_ * H + oy + dy_ - PAD) * W;
+#pragma unroll
+    for (int s = 0; s < SA; ++s) {
+      const bf16_t* src = Zero16w;
+      const int ox = ox0 + aPix[s];
+      if (ox < W) src = dY + (rowm + ox) * Kp + kt0 + aCh[s];
+      __builtin_amdgcn_global_load_lds(
+          src, lA + buf * ABYTES + (tid + s * 256) * 16, 16, 0, 0);
+    }
+#pragma unroll
+    for (int s = 0; s < SB; ++s) {
+      const bf16_t* src = Zero16w;
+      const int ix = ox0 + bPix[s];
+      if (ix >= 0 && ix < W) src = X + (rowx + ix) * CT + bCh[s];
+      __builtin_amdgcn_global_load_lds(
+          src, lB + buf * BBYTES + (tid + s * 256) * 16, 16, 0, 0);
+    }
+  };
+
+  f32x16 acc[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
+
+  // per-lane tr-read bases, as in k_conv_wgrad_patch; for the patch the
+  // 16-column half (l>>4)&1 is one whole 32-byte pixel row further on
+  const int q = (lane & 15) >> 2;
+  const int hb = (lane >> 4) & 1;
+  const int rowl = wk * 16 + (lane >> 5) * 8 + q;
+  const int acol2 = (wr * 32 + hb * 16 + (lane & 3) * 4) * 2;
+  const unsigned aB0 = (unsigned)(unsigned long long)lA +
+                       (unsigned)(rowl * BK * 2 + (acol2 ^ pt_swz(q, BK)));
+  const unsigned bB0 = (unsigned)(unsigned long long)lB +
+                       (unsigned)((rowl + hb) * CT * 2 + (lane & 3) * 8);
+
+  int buf = 0;
+  stage(0, n, oyLo + oyv, seg);
+  __syncthreads();  // drains the DMA (vmcnt 0) + barrier
+  for (int c = c0; c < c1; ++c) {
+    if (++seg == nSeg) {
+      seg = 0;
+      if (++oyv == Hv) { oyv = 0; ++n; }
+    }
+    if (c + 1 < c1) stage(buf ^ 1, n, oyLo + oyv, seg);  // DMA under the math
+    const unsigned aB = aB0 + (unsigned)(buf * ABYTES);
+    const unsigned bB = bB0 + (unsigned)(buf * BBYTES);
+
+    constexpr int RPK = 2 + 2 * NT;  // tr reads per k-step (6, 8 or 10)
+    bf16x4 aT[2][2], bT[2][NT][2];   // 2-deep k-step ring
+    auto rdk = [&](int i, int ring) {
+      const int p0 = i * WK * 16;  // first pixel of this wave's i-th k-step
+      aT[ring][0] = ds_tr16(aB + (unsigned)(p0 * BK * 2));
+      aT[ring][1] = ds_tr16(aB + (unsigned)((p0 + 4) * BK * 2));
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        bT[ring][t][0] = ds_tr16(bB + (unsigned)((p0 + 2 * t) * CT * 2));
+        bT[ring][t][1] = ds_tr16(bB + (unsigned)((p0 + 4 + 2 * t) * CT * 2));
+      }
+    };
+    rdk(0, 0);
+#pragma unroll
+    for (int i = 0; i < KSTW; ++i) {
+      const int ring = i & 1;
+      if (i + 1 < KSTW) {
+        rdk(i + 1, ring ^ 1);
+        // wait for THIS k-step's reads only
+        if constexpr (RPK == 6)
+          asm volatile("s_waitcnt lgkmcnt(6)" ::: "memory");
+        else if constexpr (RPK == 8)
+          asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
+        else
+          asm volatile("s_waitcnt lgkmcnt(10)" ::: "memory");
+      } else {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      const bf16x8 av = __builtin_shufflevector(
+          aT[ring][0], aT[ring][1], 0, 1, 2, 3, 4, 5, 6, 7);
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const bf16x8 bv = __builtin_shufflevector(
+            bT[ring][t][0], bT[ring][t][1], 0, 1, 2, 3, 4, 5, 6, 7);
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc[t],
+                                                         0, 0, 0);
+      }
+    }
+    if (c + 1 < c1) __syncthreads();  // drains DMA + joins waves
+    buf ^= 1;
+  }
+
+  // ---- epilogue: the slab scheme of k_conv_wgrad_patch, [k][c][dx] with
+  //      16 channels. D column c' of accumulator t is tap 2t + (c' >> 4),
+  //      channel c' & 15; the phantom tap dx = KS is not written. ----
+  constexpr int SLABN = G::SLABN;
+  float* slab = reinterpret_cast<float*>(smem);
+  __syncthreads();  // every wave is past its last tr read; no DMA in flight
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      const int kk = wr * 8 + rr + 4 * (lane >> 5);
+      float* dst = slab + wk * SLABN + (kk * CT + (lane & 15)) * KS + hb;
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+        if (2 * t + 1 < KS || hb == 0) dst[2 * t] = acc[t][4 * j + rr];
+    }
+    __syncthreads();
+    for (int e = tid; e < SLABN; e += 256) {
+      float v = slab[e];
+#pragma unroll
+      for (int w = 1; w < WK; ++w) v += slab[w * SLABN + e];
+      const int kk = e / (CT * KS);
+      const int rem = e - kk * (CT * KS);
+      const int cc = rem / KS;
+      const int dx = rem - cc * KS;
+      const int k = kt0 + (kk >> 3) * 32 + j * 8 + (kk & 7);
+      if (k < K && cc < C)
+        atomicAdd(&dW[(((long)k * C + cc) * KS + dy_) * KS + dx], v);
+    }
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Small-K weight gradient (K <= 4: the 64->3 / 32->3 output convs).
 // The MFMA path wastes 13/16 rows of every fragment on Kp padding there;
 // a VALU outer-product reduction is ~10x cheaper. Each block owns one
@@ -1297,13 +1555,14 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_patch(
 // sharing the octet, then atomically adds into the fp32 dW.
 // ---------------------------------------------------------------------------
 
-template <int KMAX>
+template <int KMAX, int U>
 __global__ __launch_bounds__(256, 4) void k_wgrad_smallk(
     const bf16_t* __restrict__ dY,  // (M, Kp)
     const bf16_t* __restrict__ X,   // (N,H,W,Cp)
     float* __restrict__ dW,         // (K, C, KS, KS) fp32
     int N, int H, int W, int Cp, int log2Cp, int Kp, int K, int C, int KS,
     int msplit, unsigned long long mulHW, unsigned long long mulW) {
+  static_assert(KMAX == 4, "the dY row is read as one 8-byte vector");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* red = reinterpret_cast<float*>(smem);  // [256][KMAX*8]
   const int PAD = KS / 2;
@@ -1319,56 +1578,71 @@ __global__ __launch_bounds__(256, 4) void k_wgrad_smallk(
   const long rows = (M + msplit - 1) / msplit;
   const long mstart = (long)blockIdx.y * rows;
   const long mend = min(mstart + rows, M);
-  for (long m = mstart + mr; m < mend; m += MR) {
-    unsigned n = magic_div((unsigned)m, mulHW);
-    unsigned rem = (unsigned)m - n * (unsigned)HW;
-    unsigned oy = magic_div(rem, mulW);
-    int ox = (int)(rem - oy * (unsigned)W);
-    int iy = (int)oy + dy_ - PAD, ix = ox + dx_ - PAD;
-    // branch-free halo: clamped load + zero mask — a `continue` here makes
-    // hipcc branch around the loads and drain vmcnt per element (guide §5
-    // trap 4c), serializing the whole m loop on load latency
-    const bool valid = iy >= 0 && iy < H && ix >= 0 && ix < W;
-    const int iyc = min(max(iy, 0), H - 1), ixc = min(max(ix, 0), W - 1);
-    const bf16x8 xv = *reinterpret_cast<const bf16x8*>(
-        X + (((long)((int)n * H + iyc) * W + ixc) << log2Cp) + cg * 8);
-    const bf16_t* dyp = dY + m * Kp;
-    const float mask = valid ? 1.f : 0.f;
+  // The loop is bound by load latency, not by bytes or FMAs: every
+  // iteration issues the X and dY loads of U rows before the first FMA that
+  // needs one, so U loads per thread are in flight instead of one.
+  for (long m0 = mstart + mr; m0 < mend; m0 += (long)U * MR) {
+    bf16x8 xv[U];
+    bf16x4 dv[U];
+    float mask[U];
 #pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-      const float d = mask * bf2f(dyp[k]);
+    for (int u = 0; u < U; ++u) {
+      // branch-free tail: rows past the slice re-read its last row, masked
+      const long mu = m0 + (long)u * MR;
+      const long m = min(mu, mend - 1);
+      unsigned n = magic_div((unsigned)m, mulHW);
+      unsigned rem = (unsigned)m - n * (unsigned)HW;
+      unsigned oy = magic_div(rem, mulW);
+      int ox = (int)(rem - oy * (unsigned)W);
+      int iy = (int)oy + dy_ - PAD, ix = ox + dx_ - PAD;
+      // branch-free halo: clamped load + zero mask — a `continue` here makes
+      // hipcc branch around the loads and drain vmcnt per element (guide §5
+      // trap 4c), serializing the whole m loop on load latency
+      const bool valid =
+          mu < mend && iy >= 0 && iy < H && ix >= 0 && ix < W;
+      const int iyc = min(max(iy, 0), H - 1), ixc = min(max(ix, 0), W - 1);
+      xv[u] = *reinterpret_cast<const bf16x8*>(
+          X + (((long)((int)n * H + iyc) * W + ixc) << log2Cp) + cg * 8);
+      dv[u] = *reinterpret_cast<const bf16x4*>(dY + m * Kp);  // Kp >= 16
+      mask[u] = valid ? 1.f : 0.f;
+    }
 #pragma unroll
-      for (int e = 0; e < 8; ++e) acc[k][e] += d * bf2f(xv[e]);
+    for (int u = 0; u < U; ++u) {
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k) {
+        const float d = mask[u] * bf2f(dv[u][k]);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[k][e] += d * bf2f(xv[u][e]);
+      }
     }
   }
+  // red is [k*8+e][thread]: consecutive lanes touch consecutive words, so
+  // neither the stores nor the tree conflict (thread-major rows of 32
+  // floats put every lane of a wave on two banks and made this epilogue,
+  // not the m loop, the larger part of a block's time)
+  const int tid = threadIdx.x;  // == mr * CG + cg
 #pragma unroll
   for (int k = 0; k < KMAX; ++k)
 #pragma unroll
-    for (int e = 0; e < 8; ++e)
-      red[(threadIdx.x) * (KMAX * 8) + k * 8 + e] = acc[k][e];
+    for (int e = 0; e < 8; ++e) red[(k * 8 + e) * 256 + tid] = acc[k][e];
   __syncthreads();
   // parallel tree reduce over the MR m-rows sharing each channel octet
   const int CG = Cp / 8;
   for (int s = MR / 2; s > 0; s >>= 1) {
     if (mr < s) {
 #pragma unroll
-      for (int k = 0; k < KMAX; ++k)
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          red[(mr * CG + cg) * (KMAX * 8) + k * 8 + e] +=
-              red[((mr + s) * CG + cg) * (KMAX * 8) + k * 8 + e];
+      for (int j = 0; j < KMAX * 8; ++j)
+        red[j * 256 + tid] += red[j * 256 + tid + s * CG];
     }
     __syncthreads();
   }
-  if (mr == 0) {
-    for (int k = 0; k < K && k < KMAX; ++k)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int c = cg * 8 + e;
-        if (c < C)
-          atomicAdd(&dW[(((long)k * C + c) * KS + dy_) * KS + dx_],
-                    red[cg * (KMAX * 8) + k * 8 + e]);
-      }
+  // row j of red now holds its CG octet sums in columns 0..CG-1
+  for (int t = tid; t < KMAX * 8 * CG; t += 256) {
+    const int j = t / CG, g = t - j * CG;
+    const int k = j >> 3, c = g * 8 + (j & 7);
+    if (k < K && c < C)
+      atomicAdd(&dW[(((long)k * C + c) * KS + dy_) * KS + dx_],
+                red[j * 256 + g]);
   }
 }
 
@@ -1744,9 +2018,21 @@ void launch_conv_bn(const at::Tensor& x, const at::Tensor& wp,
   HIP_CHECK_LAST();
 }
 
+// k_wgrad_smallk launch shape: blocks over (tap, m-slice) and rows in flight
+// per thread (sweep: docs/KERNELS.md, small-K section).
+constexpr int WGRAD_SMALLK_BLOCKS = 768;
+constexpr double WGRAD_SMALLK_BLOCKS_K = 0.17;
+constexpr int WGRAD_SMALLK_U = 4;
+
+// k_conv_wgrad_patch16 split-m rule: blocks = K * sqrt(work/tile), capped.
+constexpr double WGRAD_PATCH16_BLOCKS_K = 80.0;
+constexpr int WGRAD_PATCH16_BLOCKS_MAX = 1024;
+
 // (KS, Cp, Kp) classes where k_conv_wgrad_patch measured faster than
 // k_conv_wgrad on MI355X (table: docs/KERNELS.md, wgrad section).
 inline bool wgrad_patch_wins(int ks, int Cp, int Kp) {
+  // every instantiated class measured faster, the Cp = 16 tap-pair classes
+  // (k7 16->128, k7 16->32, k5 16->64, k3 16->128) included
   (void)ks; (void)Cp; (void)Kp;
   return true;
 }
@@ -1785,6 +2071,33 @@ void launch_wgrad_patch_t(const at::Tensor& dy, const at::Tensor& x,
                      W, Cp, Kp, K, C, nSeg, zero16);
 }
 
+template <int KS, int BK, int CH>
+void launch_wgrad_patch16_t(const at::Tensor& dy, const at::Tensor& x,
+                            at::Tensor& dw, const bf16_t* zero16,
+                            hipStream_t stream) {
+  using G = Patch16Geo<KS, BK, CH>;
+  const int N = x.size(0), H = x.size(1), W = x.size(2);
+  const int Kp = dy.size(3);
+  const int K = dw.size(0), C = dw.size(1);
+  const int nSeg = (W + CH - 1) / CH;
+  const int gx = Kp / BK, gy = KS;
+  // same sqrt(work/tile) rule as launch_wgrad_patch_t; the tile (BK*16*KS
+  // atomics) is 4x smaller than 64x64, so more blocks pay. Constant and cap
+  // fitted to WN_WGRAD_PATCH_BLOCKS sweeps at 112^2 and 256^2
+  // (docs/KERNELS.md).
+  const double work = (double)gx * gy * N * H * nSeg * (CH / 16);
+  int blocks = (int)(WGRAD_PATCH16_BLOCKS_K * std::sqrt(work / (BK * 16 * KS)));
+  blocks = std::min(blocks, WGRAD_PATCH16_BLOCKS_MAX);
+  if (const char* be = getenv("WN_WGRAD_PATCH_BLOCKS")) blocks = atoi(be);
+  int split = std::max(1, (blocks + gx * gy / 2) / (gx * gy));
+  split = (int)std::min<long>(split, (long)N * H * nSeg);
+  hipLaunchKernelGGL((k_conv_wgrad_patch16<KS, BK, CH>),
+                     dim3(gx, gy, split), dim3(256), (size_t)G::LDS, stream,
+                     (const bf16_t*)dy.data_ptr(),
+                     (const bf16_t*)x.data_ptr(), dw.data_ptr<float>(), N, H,
+                     W, Kp, K, C, nSeg, zero16);
+}
+
 void launch_wgrad_patch(const at::Tensor& dy, const at::Tensor& x,
                         at::Tensor& dw, int ks, int cls,
                         const bf16_t* zero16, hipStream_t stream) {
@@ -1796,14 +2109,23 @@ void launch_wgrad_patch(const at::Tensor& dy, const at::Tensor& x,
   const int force_ch = fe ? atoi(fe) : 0;
   const int W = x.size(2);
   int ch = 64;
-  if (cls == 64) {
+  if (cls == 64 || cls == 16) {
     const int pad64 = (W + 63) / 64 * 64, pad112 = (W + 111) / 112 * 112;
     ch = (pad112 < pad64) ? 112 : 64;
     if (force_ch == 64 || force_ch == 112) ch = force_ch;
   }
+  const bool bk32 = dy.size(3) == 32;  // cls 16: Kp = 32 or a multiple of 64
   auto go = [&](auto ks_const) {
     constexpr int KSV = decltype(ks_const)::value;
-    if (cls == 32)
+    if (cls == 16 && bk32 && ch == 112)
+      launch_wgrad_patch16_t<KSV, 32, 112>(dy, x, dw, zero16, stream);
+    else if (cls == 16 && bk32)
+      launch_wgrad_patch16_t<KSV, 32, 64>(dy, x, dw, zero16, stream);
+    else if (cls == 16 && ch == 112)
+      launch_wgrad_patch16_t<KSV, 64, 112>(dy, x, dw, zero16, stream);
+    else if (cls == 16)
+      launch_wgrad_patch16_t<KSV, 64, 64>(dy, x, dw, zero16, stream);
+    else if (cls == 32)
       launch_wgrad_patch_t<KSV, 32, 64>(dy, x, dw, zero16, stream);
     else if (ch == 112)
       launch_wgrad_patch_t<KSV, 64, 112>(dy, x, dw, zero16, stream);
@@ -1862,16 +2184,39 @@ void conv2d_wgrad(const at::Tensor& dy, const at::Tensor& x, at::Tensor& dw,
   hipStream_t stream0 = at::cuda::getCurrentHIPStream();
   if (K <= 4) {  // output convs (K=3): VALU outer-product path
     const int RS = (int)(ks * ks);
-    int msplit = std::max(1, 768 / RS);
+    // m-slices per tap. A block pays a fixed LDS tree reduce + atomics, so
+    // T(blocks) ~ a*work/blocks + b*blocks as for the patch kernel: blocks ~
+    // sqrt(work) with work = taps * rows * channel octets, up to one resident
+    // wave of blocks (more only queue behind it). WN_WGRAD_SMALLK_MSPLIT /
+    // WN_WGRAD_SMALLK_U override the slice count and the rows in flight per
+    // thread for A/B sweeps (docs/KERNELS.md has the sweep); read per call.
+    const double work = (double)RS * N * H * W * (Cp / 8);
+    const int blocks = std::min(
+        WGRAD_SMALLK_BLOCKS, (int)(WGRAD_SMALLK_BLOCKS_K * std::sqrt(work)));
+    int msplit = std::max(1, blocks / RS);
+    if (const char* me = getenv("WN_WGRAD_SMALLK_MSPLIT"))
+      msplit = std::max(1, atoi(me));
+    int unroll = WGRAD_SMALLK_U;
+    if (const char* ue = getenv("WN_WGRAD_SMALLK_U")) unroll = atoi(ue);
     const int MR = 256 / (Cp / 8);
     msplit = (int)std::min<long>(msplit, ((long)N * H * W + MR - 1) / MR);
-    hipLaunchKernelGGL((k_wgrad_smallk<4>), dim3(RS, msplit), dim3(256),
-                       256 * 32 * sizeof(float), stream0,
-                       (const bf16_t*)dy.data_ptr(),
-                       (const bf16_t*)x.data_ptr(), dw.data_ptr<float>(), N,
-                       H, W, Cp, log2i(Cp), Kp, K, C, (int)ks, msplit,
-                       MagicDiv::make((unsigned)(H * W)).mul,
-                       MagicDiv::make((unsigned)W).mul);
+    auto go = [&](auto u_const) {
+      constexpr int UV = decltype(u_const)::value;
+      hipLaunchKernelGGL((k_wgrad_smallk<4, UV>), dim3(RS, msplit),
+                         dim3(256), 256 * 32 * sizeof(float), stream0,
+                         (const bf16_t*)dy.data_ptr(),
+                         (const bf16_t*)x.data_ptr(), dw.data_ptr<float>(),
+                         N, H, W, Cp, log2i(Cp), Kp, K, C, (int)ks, msplit,
+                         MagicDiv::make((unsigned)(H * W)).mul,
+                         MagicDiv::make((unsigned)W).mul);
+    };
+    switch (unroll) {
+      case 1: go(std::integral_constant<int, 1>{}); break;
+      case 2: go(std::integral_constant<int, 2>{}); break;
+      case 4: go(std::integral_constant<int, 4>{}); break;
+      case 6: go(std::integral_constant<int, 6>{}); break;
+      default: TORCH_CHECK(false, "unsupported WN_WGRAD_SMALLK_U ", unroll);
+    }
     HIP_CHECK_LAST();
     return;
   }
@@ -1884,9 +2229,10 @@ void conv2d_wgrad(const at::Tensor& dy, const at::Tensor& x, at::Tensor& dw,
     return e == nullptr ? -1 : (atoi(e) != 0 ? 1 : 0);
   }();
   if (patch_mode != 0 && ks >= 3) {
-    const int cls = (Cp % 64 == 0 && Kp % 64 == 0) ? 64
-                    : (Cp == 32 && Kp == 32)       ? 32
-                                                   : 0;
+    const int cls = (Cp % 64 == 0 && Kp % 64 == 0)           ? 64
+                    : (Cp == 32 && Kp == 32)                 ? 32
+                    : (Cp == 16 && (Kp == 32 || Kp % 64 == 0)) ? 16
+                                                             : 0;
     if (cls != 0 && (patch_mode > 0 || wgrad_patch_wins((int)ks, Cp, Kp))) {
       static thread_local at::Tensor zero16p;
       if (!zero16p.defined() || zero16p.device() != x.device())

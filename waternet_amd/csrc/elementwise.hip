@@ -405,18 +405,50 @@ __global__ void k_normalize_nhwc_bwd(const bf16_t* __restrict__ dy,
 // flat variant (Clog == Cp) and channel-masked variant.
 // ---------------------------------------------------------------------------
 
+// Every atomic of a launch lands on the one output address and they
+// serialise, so the grid is capped (grid-stride loop) and a block issues
+// exactly one: fp32 per thread, f64 across the wave and, through LDS, across
+// the block.
+constexpr int SQD_MAX_BLOCKS = 512;
+
+__device__ __forceinline__ void sqdiff_block_atomic(float s,
+                                                    double* __restrict__ out) {
+  __shared__ double wsum[TPB / 64];
+  double d = (double)s;
+  for (int off = 32; off > 0; off >>= 1) d += __shfl_down(d, off, 64);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = d;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += wsum[w];
+    atomicAdd(out, t);
+  }
+}
+
 __global__ void k_sqdiff255_flat(const bf16_t* __restrict__ a,
                                  const bf16_t* __restrict__ b,
                                  double* __restrict__ out, long n) {
   float s = 0.f;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (long)gridDim.x * blockDim.x) {
+  const long t0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long nt = (long)gridDim.x * blockDim.x;
+  // 16 B body where both pointers allow it, scalar tail (or everything)
+  const bool vec =
+      (((unsigned long long)a | (unsigned long long)b) & 15ull) == 0;
+  const long nv = vec ? n / 8 : 0;
+  for (long i = t0; i < nv; i += nt) {
+    const bf16x8 av = *reinterpret_cast<const bf16x8*>(a + i * 8);
+    const bf16x8 bv = *reinterpret_cast<const bf16x8*>(b + i * 8);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float d = 255.f * (bf2f(av[e]) - bf2f(bv[e]));
+      s += d * d;
+    }
+  }
+  for (long i = nv * 8 + t0; i < n; i += nt) {
     float d = 255.f * (bf2f(a[i]) - bf2f(b[i]));
     s += d * d;
   }
-  // wave reduce then one atomic per wave
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if ((threadIdx.x & 63) == 0) atomicAdd(out, (double)s);
+  sqdiff_block_atomic(s, out);
 }
 
 __global__ void k_sqdiff255_pix(const bf16_t* __restrict__ a,
@@ -432,8 +464,7 @@ __global__ void k_sqdiff255_pix(const bf16_t* __restrict__ a,
       s += d * d;
     }
   }
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if ((threadIdx.x & 63) == 0) atomicAdd(out, (double)s);
+  sqdiff_block_atomic(s, out);
 }
 
 // backward: da = gscale * (a - b), with gscale = grad * 2*255^2/numel
@@ -738,13 +769,16 @@ at::Tensor sqdiff255_sum(const at::Tensor& a, const at::Tensor& b,
   const long Cp = a.size(3);
   if (Clog == Cp) {
     const long n = a.numel();
-    hipLaunchKernelGGL(k_sqdiff255_flat, dim3(grid1d(n)), dim3(TPB), 0,
+    hipLaunchKernelGGL(k_sqdiff255_flat,
+                       dim3(grid1d((n + 7) / 8, TPB, SQD_MAX_BLOCKS)),
+                       dim3(TPB), 0,
                        cur_stream(), (const bf16_t*)a.data_ptr(),
                        (const bf16_t*)b.data_ptr(), out.data_ptr<double>(),
                        n);
   } else {
     const long NHW = a.numel() / Cp;
-    hipLaunchKernelGGL(k_sqdiff255_pix, dim3(grid1d(NHW)), dim3(TPB), 0,
+    hipLaunchKernelGGL(k_sqdiff255_pix,
+                       dim3(grid1d(NHW, TPB, SQD_MAX_BLOCKS)), dim3(TPB), 0,
                        cur_stream(), (const bf16_t*)a.data_ptr(),
                        (const bf16_t*)b.data_ptr(), out.data_ptr<double>(),
                        NHW, (int)Clog, (int)Cp);
