@@ -62,17 +62,21 @@ def test_conv_fwd_parity(ext, ks, C, K):
 
 @pytest.mark.parametrize("ks,C,K", [(5, 128, 128), (7, 64, 64),
                                     (3, 64, 128)])
-def test_conv_fwd_parity_bigM(ext, ks, C, K):
-    """Big-M shapes dispatch to the 8-wave 256-row phase-split kernel
-    (M >= 16384); verify parity there too."""
+def test_conv_fwd_parity_splitk_gz3(ext, ks, C, K):
+    """N=2, 96x96 (M = 18432) at these channel counts has base = 144 blocks
+    and nk >= 16, so all three shapes run split-K with gz = 3, not the
+    8-wave igemm8 (which needs gz == 1; tests/test_gpu_conv_exact.py covers
+    it). Random-data parity of that split-K tier."""
     from waternet_amd.ops.conv import pow2_channels
 
     torch.manual_seed(4)
-    N, H, W = 2, 96, 96  # M = 18432 >= 16384
+    N, H, W = 2, 96, 96
     x = torch.rand(N, C, H, W, device=DEV)
     w = torch.randn(K, C, ks, ks, device=DEV) * 0.05
     b = torch.randn(K, device=DEV) * 0.1
     Cp, Kp = pow2_channels(C), pow2_channels(K)
+    assert (tuple(ext.conv2d_fwd_plan(N, H, W, Cp, Kp, ks))
+            == ("splitk", 64 if Kp == 64 else 128, 3))
     wp = ext.pack_weight_fwd(w.contiguous(), Kp, Cp)
     y = ext.conv2d_fwd(to_nhwc_bf16(x, Cp), wp, b, ks, Kp, K, 1)
     got = from_nhwc(y, K)

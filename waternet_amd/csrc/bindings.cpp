@@ -1,12 +1,16 @@
 // Python bindings for the waternet_amd CDNA4 kernel library.
 #include <torch/extension.h>
 
+#include <string>
+#include <tuple>
 #include <vector>
 
 // conv_mfma.hip
 at::Tensor conv2d_fwd(const at::Tensor& x, const at::Tensor& wp,
                       const c10::optional<at::Tensor>& bias, int64_t ks,
                       int64_t Kp, int64_t Klog, int64_t act);
+std::tuple<std::string, int64_t, int64_t> conv2d_fwd_plan(
+    int64_t N, int64_t H, int64_t W, int64_t Cp, int64_t Kp, int64_t ks);
 void conv2d_wgrad(const at::Tensor& dy, const at::Tensor& x, at::Tensor& dw,
                   int64_t ks);
 void bias_grad(const at::Tensor& dy, at::Tensor& db);
@@ -70,7 +74,9 @@ std::vector<at::Tensor> preprocess_all(const at::Tensor& raw_u8);
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_fwd", &conv2d_fwd,
         "NHWC bf16 implicit-GEMM conv fwd (MFMA), fused bias+act");
-  m.def("conv2d_wgrad", &conv2d_wgrad, "conv weight grad into NCHW fp32");
+  m.def("conv2d_fwd_plan", &conv2d_fwd_plan,
+        "dispatch decision of conv2d_fwd for a shape: (kernel, BN, gz)");
+  m.def("conv2d_wgrad", &conv2d_wgrad,"conv weight grad into NCHW fp32");
   m.def("bias_grad", &bias_grad, "bias grad (column sum)");
   m.def("pack_weight_fwd", &pack_weight_fwd);
   m.def("pack_weight_dgrad", &pack_weight_dgrad);

@@ -344,8 +344,11 @@ __global__ __launch_bounds__(512, 1) void k_conv_igemm8(
   const long M = (long)N * H * W;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  bf16_t* lA = reinterpret_cast<bf16_t*>(smem);   // 3 x LA
-  bf16_t* lB = lA + 3 * LA;                       // 3 x LB8
+  // the B buffers start after RING A buffers (the launch sizes the
+  // allocation by the same ring depth)
+  constexpr int RING = (VAR == 3) ? 4 : 3;
+  bf16_t* lA = reinterpret_cast<bf16_t*>(smem);   // RING x LA
+  bf16_t* lB = lA + RING * LA;                    // RING x LB8
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -450,7 +453,6 @@ __global__ __launch_bounds__(512, 1) void k_conv_igemm8(
   const int nk = (KG + 31) / 32;
   const int lg = lane >> 4, li = lane & 15;
   constexpr int GPS = ASLOT + BSLOT;  // 3 glds per thread per stage
-  constexpr int RING = (VAR == 3) ? 4 : 3;
   constexpr int AHEAD = RING - 2;  // tiles left in flight at the wait
   constexpr bool PRIO = (VAR != 1);
   constexpr int NPH = (VAR == 2) ? 4 : 2;  // M-fragment phases per K-step
@@ -1885,6 +1887,52 @@ inline int log2i(int v) {
   return l;
 }
 
+// Which forward kernel a conv shape runs on, and on what grid. The single
+// source of the dispatch rule: launch_conv_bn launches what this returns and
+// conv2d_fwd_plan reports it to the tests.
+enum ConvTier { TIER_IGEMM = 0, TIER_SPLITK = 1, TIER_IGEMM8 = 2 };
+
+struct ConvPlan {
+  ConvTier tier;
+  int BN;      // N tile: 16 / 32 / 64 / 128
+  int gx, gy;  // 128-row M blocks, BN-wide N blocks
+  int nk;      // 32-wide K tiles
+  int gz;      // split-K slices (1 unless tier == TIER_SPLITK)
+};
+
+inline ConvPlan conv_plan(long M, int Cp, int Kp, int ks) {
+  ConvPlan p;
+  p.BN = Kp >= 128 ? 128 : Kp == 64 ? 64 : Kp == 32 ? 32 : 16;
+  p.gx = (int)((M + 127) / 128);
+  p.gy = (Kp + p.BN - 1) / p.BN;
+  p.nk = (ks * ks * Cp + 31) / 32;
+  // Small-M shapes (e.g. VGG 14^2/7^2 layers at bs=16) leave most of the
+  // 256 CUs idle; split the K loop across gz slices into fp32 partials,
+  // then finalize bias+act+bf16 in a second tiny pass.
+  const int base = p.gx * p.gy;
+  int gz = 1;
+  if (base < 320 && p.nk >= 16)
+    gz = std::min(std::max(1, 512 / base), p.nk / 4);
+  // finalize's unrolled reads tolerate more slabs for the tiniest
+  // (grid-limited) shapes; snap >8 to the instantiated 12/16 variants
+  gz = std::min(gz, base < 64 ? 16 : 8);
+  if (gz > 8) gz = (gz >= 16) ? 16 : 12;
+  p.gz = gz;
+  p.tier = TIER_IGEMM;
+  if (gz > 1) {
+    p.tier = TIER_SPLITK;
+  } else if (p.BN >= 64) {
+    static const long m8_thresh = [] {
+      // A/B override: the M threshold above which the 8-wave 256-row
+      // igemm8 is used instead of the 4-wave 128-row igemm
+      const char* e = getenv("WN_IGEMM8_MTHRESH");
+      return e ? atol(e) : 16384L;
+    }();
+    if (M >= m8_thresh) p.tier = TIER_IGEMM8;
+  }
+  return p;
+}
+
 template <int KS>
 void launch_conv_bn(const at::Tensor& x, const at::Tensor& wp,
                     const c10::optional<at::Tensor>& bias, at::Tensor& y,
@@ -1894,8 +1942,8 @@ void launch_conv_bn(const at::Tensor& x, const at::Tensor& wp,
   const long M = (long)N * H * W;
   const float* bptr =
       bias.has_value() ? bias->data_ptr<float>() : nullptr;
-  const int gx = (int)((M + 127) / 128);
-  const int nk = (KS * KS * Cp + 31) / 32;
+  const ConvPlan plan = conv_plan(M, Cp, Kp, KS);
+  const int gx = plan.gx, gy = plan.gy, gz = plan.gz;
   // 16 B zero source for glds halo/pad lanes (per-device, created once)
   static thread_local at::Tensor zero16;
   if (!zero16.defined() || zero16.device() != x.device())
@@ -1904,22 +1952,11 @@ void launch_conv_bn(const at::Tensor& x, const at::Tensor& wp,
 
   auto launch = [&](auto bn_const) {
     constexpr int BN = decltype(bn_const)::value;
-    const int gy = (Kp + BN - 1) / BN;
     constexpr int NBS = (BN * 4 + 255) / 256;
     constexpr int DKH = (BN <= 32) ? 2 : 1;
     const size_t lds =
         (2 * DKH * 128 * 32 + 2 * DKH * NBS * 256 * 8) * sizeof(bf16_t);
-    // Small-M shapes (e.g. VGG 14^2/7^2 layers at bs=16) leave most of the
-    // 256 CUs idle; split the K loop across gz slices into fp32 partials,
-    // then finalize bias+act+bf16 in a second tiny pass.
-    const int base = gx * gy;
-    int gz = 1;
-    if (base < 320 && nk >= 16) gz = std::min(std::max(1, 512 / base), nk / 4);
-    // finalize's unrolled reads tolerate more slabs for the tiniest
-    // (grid-limited) shapes; snap >8 to the instantiated 12/16 variants
-    gz = std::min(gz, base < 64 ? 16 : 8);
-    if (gz > 8) gz = (gz >= 16) ? 16 : 12;
-    if (gz > 1) {
+    if (plan.tier == TIER_SPLITK) {
       auto y32 = at::empty({gz, M, (long)Kp}, x.options().dtype(at::kFloat));
       const size_t lds5 =
           (5 * 128 * 32 + 5 * NBS * 256 * 8) * sizeof(bf16_t);
@@ -1951,13 +1988,7 @@ void launch_conv_bn(const at::Tensor& x, const at::Tensor& wp,
     } else {
       bool done8 = false;
       if constexpr (BN >= 64) {
-        static const long m8_thresh = [] {
-          // A/B override: the M threshold above which the 8-wave 256-row
-          // igemm8 is used instead of the 4-wave 128-row igemm
-          const char* e = getenv("WN_IGEMM8_MTHRESH");
-          return e ? atol(e) : 16384L;
-        }();
-        if (M >= m8_thresh) {  // big-M: 8-wave 256-row phase-split kernel
+        if (plan.tier == TIER_IGEMM8) {  // big-M: 8-wave 256-row phase-split
           static const int var = [] {
             const char* e = getenv("WN_IGEMM8_VAR");
             return e ? atoi(e) : 0;
@@ -2007,14 +2038,12 @@ void launch_conv_bn(const at::Tensor& x, const at::Tensor& wp,
                            Kp, Klog, act, zptr);
     }
   };
-  if (Kp >= 128)
-    launch(std::integral_constant<int, 128>{});
-  else if (Kp == 64)
-    launch(std::integral_constant<int, 64>{});
-  else if (Kp == 32)
-    launch(std::integral_constant<int, 32>{});
-  else
-    launch(std::integral_constant<int, 16>{});
+  switch (plan.BN) {
+    case 128: launch(std::integral_constant<int, 128>{}); break;
+    case 64: launch(std::integral_constant<int, 64>{}); break;
+    case 32: launch(std::integral_constant<int, 32>{}); break;
+    default: launch(std::integral_constant<int, 16>{});
+  }
   HIP_CHECK_LAST();
 }
 
@@ -2141,6 +2170,20 @@ void launch_wgrad_patch(const at::Tensor& dy, const at::Tensor& x,
 }
 
 }  // namespace
+
+// The dispatch decision conv2d_fwd would take for an (N,H,W,Cp) input and Kp
+// output channels: (kernel, BN, gz). Host only: launches nothing and touches
+// no device memory.
+std::tuple<std::string, int64_t, int64_t> conv2d_fwd_plan(
+    int64_t N, int64_t H, int64_t W, int64_t Cp, int64_t Kp, int64_t ks) {
+  TORCH_CHECK(ks == 1 || ks == 3 || ks == 5 || ks == 7,
+              "unsupported kernel size ", ks);
+  const ConvPlan p = conv_plan((long)(N * H * W), (int)Cp, (int)Kp, (int)ks);
+  const char* name = p.tier == TIER_SPLITK   ? "splitk"
+                     : p.tier == TIER_IGEMM8 ? "igemm8"
+                                             : "igemm";
+  return {name, p.BN, p.gz};
+}
 
 at::Tensor conv2d_fwd(const at::Tensor& x, const at::Tensor& wp,
                       const c10::optional<at::Tensor>& bias, int64_t ks,
