@@ -23,6 +23,9 @@ Extensions (do not break reference invocations):
   --full-state     also save optimizer/scheduler/epoch sidecar for resume
   --engine         auto | fast | eager (auto = fast on GPU, eager on CPU)
   --no-graph       disable hipGraph capture in the fast engine
+  --device-cache   fast engine: decode/resize the dataset once, keep the
+                   uint8 pairs on the GPU and gather + augment each
+                   minibatch there (waternet_amd.data.device_cache)
 
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N
 train.py ...` — one rank per GPU, RCCL all-reduce gradient sync
@@ -40,6 +43,11 @@ import numpy as np
 import torch
 
 from waternet_amd.data.dataset import SyntheticUIEBDataset, UIEBDataset
+from waternet_amd.data.device_cache import (
+    DeviceEpochSource,
+    build_cache,
+    identity_pair,
+)
 from waternet_amd.engine.trainer import (
     TRAIN_METRICS_NAMES,
     VAL_METRICS_NAMES,
@@ -83,6 +91,11 @@ def parse_args(argv=None):
                              "PyTorch on CPU")
     parser.add_argument("--no-graph", action="store_true",
                         help="fast engine: disable hipGraph capture")
+    parser.add_argument("--device-cache", action="store_true",
+                        help="fast engine: decode and resize every image "
+                             "once, keep the uint8 pairs on the GPU and "
+                             "gather + augment each minibatch with one HIP "
+                             "kernel instead of the DataLoaders")
     return parser.parse_args(argv)
 
 
@@ -153,6 +166,49 @@ def _train_epoch_fast(engine, loader, batch_size, device, epoch_num,
     }
 
 
+def _train_epoch_cached(engine, source, epoch_num, total_epochs, progress):
+    """_train_epoch_fast fed from a DeviceEpochSource: per step one gather
+    launch into the static buffers, no host-to-device traffic."""
+    snap = engine.metrics_snapshot()
+    t0 = timer()
+    iterator = source.epoch(epoch_num)
+    if progress:
+        try:
+            from tqdm import tqdm
+
+            iterator = tqdm(iterator, total=len(source), ascii=True,
+                            desc=f"Epoch {epoch_num + 1}/{total_epochs}",
+                            bar_format="{l_bar}{bar:20}{r_bar}")
+        except ImportError:
+            pass
+    n_images = 0
+    for idx, codes, n in iterator:
+        n_images += n
+        raw, ref = engine.load_batch_cached(source.cache_raw,
+                                            source.cache_ref, idx, codes)
+        if n == engine.bs:
+            engine.step()
+        else:  # ragged tail batch: eager step at its true size
+            engine.step_batch(raw, ref)
+    m = engine.metrics_since(snap)  # ONE host sync per epoch (joins the GPU)
+    wall = timer() - t0
+    if progress and n_images:
+        print(f"    [fast] epoch train wall {wall:.3f}s = "
+              f"{n_images / wall:.0f} img/s")
+    return {
+        "mse": m["mse255"], "ssim": m["ssim"], "psnr": m["psnr"],
+        "perceptual_loss": m["perceptual"], "loss": m["loss"],
+    }
+
+
+def _eval_epoch_cached(engine, source):
+    engine.reset_eval()
+    for idx, codes, _ in source.epoch(0):
+        engine.eval_batch(*engine.load_batch_cached(
+            source.cache_raw, source.cache_ref, idx, codes))
+    return engine.eval_metrics()
+
+
 def _eval_epoch_fast(engine, loader, device):
     engine.reset_eval()
     for batch in loader:
@@ -184,6 +240,12 @@ def main(argv=None):
         device = torch.device("cpu")
 
     use_fast = _select_engine(args, device)
+    if args.device_cache and not use_fast:
+        raise SystemExit(
+            "--device-cache requires the fast engine (a ROCm GPU with the "
+            "native extension): the cache lives on the GPU and feeds "
+            "FastStepEngine's input buffers; drop the flag to train with "
+            "the eager engine")
 
     # Savedir: training/<max numbered subdir + 1>  (train.py:210-221)
     outputdir.mkdir(exist_ok=True)
@@ -209,6 +271,9 @@ def main(argv=None):
             im_height=args.height,
             im_width=args.width,
             raw_mode=use_fast,
+            # the device cache stores un-augmented pairs; the gather
+            # kernel applies the same joint flip/rot90 per step
+            transform=identity_pair if args.device_cache else None,
         )
         split = [800, 90]
     if len(dataset) != sum(split):
@@ -223,17 +288,33 @@ def main(argv=None):
     if num_workers is None:
         num_workers = min(4, os.cpu_count() or 1) if use_fast else 0
 
-    train_loader = torch.utils.data.DataLoader(
-        train_dataset, batch_size=args.batch_size, shuffle=args.shuffle,
-        num_workers=num_workers, pin_memory=device.type == "cuda",
-        persistent_workers=num_workers > 0,
-    )
-    val_loader = torch.utils.data.DataLoader(
-        val_dataset, batch_size=args.batch_size,
-        num_workers=num_workers,
-        pin_memory=device.type == "cuda",
-        persistent_workers=num_workers > 0,
-    )
+    train_loader = val_loader = train_source = val_source = None
+    if args.device_cache:
+        # this rank's train shard + the full val split, decoded once
+        train_source = DeviceEpochSource(
+            *build_cache(train_dataset, device, num_workers),
+            batch_size=args.batch_size, shuffle=args.shuffle,
+            # UIEBDataset augments, SyntheticUIEBDataset does not
+            augment=args.synthetic is None,
+            seed=args.seed if args.seed is not None else 0,
+            rank=dist_env.rank,
+        )
+        val_source = DeviceEpochSource(
+            *build_cache(val_dataset, device, num_workers),
+            batch_size=args.batch_size, shuffle=False, augment=False,
+        )
+    else:
+        train_loader = torch.utils.data.DataLoader(
+            train_dataset, batch_size=args.batch_size, shuffle=args.shuffle,
+            num_workers=num_workers, pin_memory=device.type == "cuda",
+            persistent_workers=num_workers > 0,
+        )
+        val_loader = torch.utils.data.DataLoader(
+            val_dataset, batch_size=args.batch_size,
+            num_workers=num_workers,
+            pin_memory=device.type == "cuda",
+            persistent_workers=num_workers > 0,
+        )
 
     if rank0:
         print(f"Using device: {device} "
@@ -322,7 +403,13 @@ def main(argv=None):
     saved_val = {k: [] for k in VAL_METRICS_NAMES}
 
     for epoch in range(start_epoch, args.epochs):
-        if use_fast:
+        if train_source is not None:
+            train_metrics = _train_epoch_cached(
+                engine, train_source, epoch_num=epoch,
+                total_epochs=args.epochs, progress=rank0,
+            )
+            val_metrics = _eval_epoch_cached(engine, val_source)
+        elif use_fast:
             train_metrics = _train_epoch_fast(
                 engine, train_loader, args.batch_size, device,
                 epoch_num=epoch, total_epochs=args.epochs, progress=rank0,
@@ -387,18 +474,17 @@ def main(argv=None):
         np.savetxt(savedir / "metrics-val.csv", val_arr, fmt="%f",
                    delimiter=",", comments="",
                    header=",".join(VAL_METRICS_NAMES))
+        config = {
+            "epochs": args.epochs,
+            "batch_size": args.batch_size,
+            "im_height": args.height,
+            "im_width": args.width,
+            "weights": args.weights,
+        }
+        if args.device_cache:
+            config["device_cache"] = True
         with open(savedir / "config.json", "w") as f:
-            json.dump(
-                {
-                    "epochs": args.epochs,
-                    "batch_size": args.batch_size,
-                    "im_height": args.height,
-                    "im_width": args.width,
-                    "weights": args.weights,
-                },
-                f,
-                indent=4,
-            )
+            json.dump(config, f, indent=4)
         print(f"Metrics and weights saved to {savedir}")
         print(f"Total time: {timer() - start_ts}s")
 

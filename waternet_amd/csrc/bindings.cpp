@@ -55,6 +55,10 @@ at::Tensor normalize_nhwc_bwd(const at::Tensor& dy);
 void adam_step(at::Tensor& p, const at::Tensor& g, at::Tensor& m,
                at::Tensor& v, const at::Tensor& lr_buf, double b1, double b2,
                double eps, at::Tensor& step_buf);
+void gather_augment_u8(const at::Tensor& cache_raw,
+                       const at::Tensor& cache_ref, const at::Tensor& idx,
+                       const at::Tensor& codes, at::Tensor& out_raw,
+                       at::Tensor& out_ref, bool allow_transpose);
 
 // pool.hip
 std::vector<at::Tensor> maxpool2x2_fwd(const at::Tensor& x);
@@ -103,6 +107,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("u8_to_nhwc", &u8_to_nhwc);
   m.def("normalize_nhwc_fwd", &normalize_nhwc_fwd);
   m.def("normalize_nhwc_bwd", &normalize_nhwc_bwd);
+  m.def("gather_augment_u8", &gather_augment_u8,
+        "cached uint8 HWC pairs -> batch slots under flip/rot90 codes, "
+        "written in place",
+        pybind11::arg("cache_raw"), pybind11::arg("cache_ref"),
+        pybind11::arg("idx"), pybind11::arg("codes"),
+        pybind11::arg("out_raw"), pybind11::arg("out_ref"),
+        pybind11::arg("allow_transpose") = false);
   m.def("maxpool2x2_fwd", &maxpool2x2_fwd);
   m.def("maxpool2x2_bwd", &maxpool2x2_bwd);
   m.def("ssim_sum", &ssim_sum);

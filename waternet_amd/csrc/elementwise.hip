@@ -8,6 +8,7 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "common.h"
+#include "gather_augment.h"
 
 namespace {
 inline hipStream_t cur_stream() { return at::cuda::getCurrentHIPStream(); }
@@ -837,5 +838,99 @@ void adam_step(at::Tensor& p, const at::Tensor& g, at::Tensor& m,
                      m.data_ptr<float>(), v.data_ptr<float>(), n,
                      lr_buf.data_ptr<float>(), (float)b1, (float)b2,
                      (float)eps, step_buf.data_ptr<int>());
+  HIP_CHECK_LAST();
+}
+
+// ---------------------------------------------------------------------------
+// Device-resident dataset cache: gather a minibatch of cached uint8 HWC
+// pairs into the engine's input buffers under the joint flip/rot90
+// augmentation (data/augment.py PairedAugment), one launch for raw + ref.
+// grid = (tiles, B, 2): blockIdx.y is the batch slot (its index and code
+// are block-uniform), blockIdx.z picks raw / ref. Index math and the LDS
+// tile scheme: gather_augment.h.
+// ---------------------------------------------------------------------------
+
+__global__ __launch_bounds__(GA_THREADS) void k_gather_augment_u8(
+    const uint8_t* __restrict__ cache_raw,
+    const uint8_t* __restrict__ cache_ref, const int* __restrict__ idx,
+    const int* __restrict__ codes, uint8_t* __restrict__ out_raw,
+    uint8_t* __restrict__ out_ref, int Nc, int H, int W, int tiles_x,
+    int allow_transpose) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[GA_LDS_BYTES];
+  const int slot = blockIdx.y;
+  // unsigned min: a negative or too-large index can never read outside
+  // the cache (the Python layer validates on the host before upload)
+  const unsigned n = min((unsigned)idx[slot], (unsigned)(Nc - 1));
+  const int tile_y = blockIdx.x / tiles_x;
+  const int tile_x = blockIdx.x - tile_y * tiles_x;
+  const GaTile t = ga_make_tile(codes[slot], allow_transpose != 0, H, W,
+                                tile_y, tile_x);
+  const size_t img = (size_t)H * W * 3;
+  const uint8_t* src = (blockIdx.z ? cache_ref : cache_raw) + n * img;
+  uint8_t* dst = (blockIdx.z ? out_ref : out_raw) + (size_t)slot * img;
+  ga_load_tile(t, threadIdx.x, W, src, lds);
+  __syncthreads();
+  ga_store_tile(t, threadIdx.x, W, lds, dst);
+}
+
+void gather_augment_u8(const at::Tensor& cache_raw,
+                       const at::Tensor& cache_ref, const at::Tensor& idx,
+                       const at::Tensor& codes, at::Tensor& out_raw,
+                       at::Tensor& out_ref, bool allow_transpose) {
+  TORCH_CHECK(cache_raw.is_cuda() && cache_ref.is_cuda() && idx.is_cuda() &&
+                  codes.is_cuda() && out_raw.is_cuda() && out_ref.is_cuda(),
+              "gather_augment_u8: all tensors must be on the GPU");
+  const auto dev = cache_raw.device();
+  TORCH_CHECK(cache_ref.device() == dev && idx.device() == dev &&
+                  codes.device() == dev && out_raw.device() == dev &&
+                  out_ref.device() == dev,
+              "gather_augment_u8: all tensors must be on the same device");
+  TORCH_CHECK(cache_raw.dtype() == at::kByte &&
+                  cache_ref.dtype() == at::kByte &&
+                  out_raw.dtype() == at::kByte && out_ref.dtype() == at::kByte,
+              "gather_augment_u8: caches and outputs must be uint8");
+  TORCH_CHECK(idx.dtype() == at::kInt && codes.dtype() == at::kInt,
+              "gather_augment_u8: idx and codes must be int32");
+  TORCH_CHECK(cache_raw.dim() == 4 && cache_raw.size(3) == 3 &&
+                  cache_raw.size(0) >= 1,
+              "gather_augment_u8: cache must be (Nc>=1, H, W, 3)");
+  TORCH_CHECK(cache_ref.sizes() == cache_raw.sizes(),
+              "gather_augment_u8: cache_raw / cache_ref shapes differ");
+  TORCH_CHECK(idx.dim() == 1 && codes.dim() == 1 &&
+                  idx.size(0) == codes.size(0),
+              "gather_augment_u8: idx and codes must both be (B,)");
+  const long Nc = cache_raw.size(0), H = cache_raw.size(1),
+             W = cache_raw.size(2), B = idx.size(0);
+  TORCH_CHECK(out_raw.dim() == 4 && out_raw.size(0) == B &&
+                  out_raw.size(1) == H && out_raw.size(2) == W &&
+                  out_raw.size(3) == 3 && out_ref.sizes() == out_raw.sizes(),
+              "gather_augment_u8: outputs must be (B, H, W, 3) matching "
+              "the cache and idx");
+  TORCH_CHECK(cache_raw.is_contiguous() && cache_ref.is_contiguous() &&
+                  idx.is_contiguous() && codes.is_contiguous() &&
+                  out_raw.is_contiguous() && out_ref.is_contiguous(),
+              "gather_augment_u8: all tensors must be contiguous");
+  TORCH_CHECK(H % 8 == 0 && W % 8 == 0,
+              "gather_augment_u8: H and W must be divisible by 8");
+  TORCH_CHECK(!allow_transpose || H == W,
+              "gather_augment_u8: allow_transpose (odd rot90 k) needs H == W");
+  TORCH_CHECK(Nc < (1L << 31) && B <= 65535,
+              "gather_augment_u8: Nc < 2^31 and B <= 65535");
+  // dword accesses: image bases are multiples of 192 B off these pointers
+  TORCH_CHECK(((uintptr_t)cache_raw.data_ptr() | (uintptr_t)cache_ref.data_ptr() |
+               (uintptr_t)out_raw.data_ptr() | (uintptr_t)out_ref.data_ptr()) %
+                      4 == 0,
+              "gather_augment_u8: tensors must be 4-byte aligned");
+  if (B == 0) return;
+  const int tiles_x = (int)((W + GA_TILE - 1) / GA_TILE);
+  const int tiles_y = (int)((H + GA_TILE - 1) / GA_TILE);
+  hipLaunchKernelGGL(k_gather_augment_u8,
+                     dim3((unsigned)(tiles_x * tiles_y), (unsigned)B, 2),
+                     dim3(GA_THREADS), 0, cur_stream(),
+                     cache_raw.data_ptr<uint8_t>(),
+                     cache_ref.data_ptr<uint8_t>(), idx.data_ptr<int>(),
+                     codes.data_ptr<int>(), out_raw.data_ptr<uint8_t>(),
+                     out_ref.data_ptr<uint8_t>(), (int)Nc, (int)H, (int)W,
+                     tiles_x, (int)allow_transpose);
   HIP_CHECK_LAST();
 }

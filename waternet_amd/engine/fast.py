@@ -272,6 +272,26 @@ class FastStepEngine:
         self.raw_static.copy_(raw_host_u8, non_blocking=True)
         self.ref_static.copy_(ref_host_u8, non_blocking=True)
 
+    def load_batch_cached(self, cache_raw, cache_ref, idx, codes):
+        """Device-side twin of load_batch: one HIP launch on the current
+        stream gathers cache[idx] under the flip/rot90 `codes`
+        (data/device_cache.py) for raw and ref. A full batch lands in the
+        static buffers (outside the captured graph, where the two H2D
+        copies sit otherwise) — follow with step(); a short one lands in a
+        tail-sized temporary — pass it to step_batch / eval_batch. Returns
+        the (raw, ref) pair that was written."""
+        from waternet_amd.data.device_cache import gather_augment
+
+        n = idx.shape[0]
+        if n == self.bs:
+            raw, ref = self.raw_static, self.ref_static
+        else:
+            raw = torch.empty((n, self.h, self.w, 3), dtype=torch.uint8,
+                              device=self.device)
+            ref = torch.empty_like(raw)
+        gather_augment(cache_raw, cache_ref, idx, codes, raw, ref)
+        return raw, ref
+
     def step(self):
         """One training step on the data currently in the static buffers
         (graph replay at steady state)."""
