@@ -20,7 +20,9 @@ CSRC = ROOT / "waternet_amd" / "csrc"
 
 sources = [
     str(CSRC / "bindings.cpp"),
-    str(CSRC / "conv_mfma.hip"),
+    str(CSRC / "conv_fwd.hip"),
+    str(CSRC / "conv_wgrad.hip"),
+    str(CSRC / "conv_pack.hip"),
     str(CSRC / "elementwise.hip"),
     str(CSRC / "pool.hip"),
     str(CSRC / "ssim.hip"),

@@ -54,7 +54,7 @@ def pow2(c):
 
 def patch_class(ks, Cp, Kp):
     """Channel class k_conv_wgrad_patch is instantiated for (0 = none);
-    mirrors conv2d_wgrad in csrc/conv_mfma.hip."""
+    mirrors conv2d_wgrad in csrc/conv_wgrad.hip."""
     if ks < 3:
         return 0
     if Cp % 64 == 0 and Kp % 64 == 0:

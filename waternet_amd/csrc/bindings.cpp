@@ -5,7 +5,7 @@
 #include <tuple>
 #include <vector>
 
-// conv_mfma.hip
+// conv_fwd.hip / conv_wgrad.hip / conv_pack.hip
 at::Tensor conv2d_fwd(const at::Tensor& x, const at::Tensor& wp,
                       const c10::optional<at::Tensor>& bias, int64_t ks,
                       int64_t Kp, int64_t Klog, int64_t act);

@@ -1,15 +1,7 @@
-// MFMA implicit-GEMM convolution engine for gfx950 (CDNA4).
-//
-// Replaces the reference's implicit cuDNN conv launches (SURVEY §2.2
-// K2-K9, K12-K14, K17) with hand-written NHWC bf16 kernels:
-//   - k_conv_igemm<BN,KS,SPLITK>: stride-1 same-pad conv fwd as implicit
-//     GEMM (M = N*H*W rows, N = output channels, K = R*S*Cp) on
-//     v_mfma_f32_16x16x32_bf16 with fused bias + ReLU/Sigmoid epilogue and
-//     global_load_lds staging; SPLITK slices the K loop over gridDim.z into
-//     fp32 slabs (3-deep LDS ring, counted vmcnt) for small-M shapes.
-//     Also runs dgrad (conv of dY with rotated/transposed packed weights).
-//   - k_conv_igemm8<BN,KS>: 8-wave 256-row phase-split variant for big-M
-//     shapes (setprio-wrapped MFMA phases, counted vmcnt).
+// Weight- and bias-gradient kernels of the MFMA conv engine for gfx950
+// (CDNA4); forward / dgrad are in conv_fwd.hip. Replaces the reference's
+// implicit cuDNN backward-filter launches with hand-written NHWC bf16
+// kernels:
 //   - k_conv_wgrad<KS,BK,CH>: weight gradient as reduction GEMM over M,
 //     m-major LDS images + ds_read_b64_tr_b16 hardware transpose reads,
 //     fp32 atomic accumulation into the NCHW fp32 grad tensor.
@@ -17,602 +9,15 @@
 //     32/64-multiple channel classes: one X row segment staged once, the
 //     KS dx taps taken by row-shifted tr reads, LDS-transposed epilogue so
 //     the atomics are contiguous.
+//   - k_conv_wgrad_patch16<KS,BK,CH>: the same for Cp = 16, two taps per
+//     MFMA.
 //   - k_wgrad_smallk: VALU outer-product path for K <= 4 output convs.
 //   - k_bias_grad(+_reduce): slab-partial column sums of dY.
-//   - k_pack_fwd / k_pack_dgrad / k_pack_all: NCHW fp32 masters -> bf16
-//     packed [Kp][R*S*Cp] (fwd) and rotated [Cp][R*S*Kp] (dgrad) layouts.
-//
-// Design notes (MI355X):
-//   - igemm LDS tiles are FRAGMENT-MAJOR: slot (mf, kb, i) holds the 8
-//     bf16 the MFMA lane (kb,i) consumes, so the lane-linear glds image and
-//     ds_read_b128 fragment loads are bank-conflict-free without swizzles.
-//   - Cp (physical channels) is a power of two >= 16; pad channels are
-//     zero by construction everywhere, so no channel masking in the GEMM.
-//
-// WN_MFMA_KMAP: fragment K mapping, measured by probe_mfma.hip — 0 on this
-// hardware (lane group g consumes reduction elements k = g*8+e).
+//   - k_probe_tr(+_raw): ds_read_b64_tr_b16 semantics probes for the tests.
+// Every kernel with dynamic LDS takes its tile constants from a Geo struct,
+// and its launch takes LDS_BYTES from the same struct.
 
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-
-#include "common.h"
-
-#ifndef WN_MFMA_KMAP
-#define WN_MFMA_KMAP 0
-#endif
-
-// ---------------------------------------------------------------------------
-// Forward / dgrad implicit GEMM
-// ---------------------------------------------------------------------------
-
-template <int BN, int KS, bool SPLITK = false>
-__global__ __launch_bounds__(256, 2) void k_conv_igemm(
-    const bf16_t* __restrict__ X,   // (N, H, W, Cp)
-    const bf16_t* __restrict__ Wp,  // [Kp][RS*Cp] k-major packed
-    const float* __restrict__ Bias, // [>=Klog] or nullptr
-    bf16_t* __restrict__ Y,         // (N, H, W, Kp)
-    int N, int H, int W, int Cp, int log2Cp, int Kp, int Klog, int act,
-    const bf16_t* __restrict__ Zero16,    // 16 B of zeros (halo/pad source)
-    float* __restrict__ Y32 = nullptr) {  // SPLITK: fp32 partial slabs.
-                                        // NOT pre-zeroed (at::empty): every
-                                        // slice block fully stores its m<M
-                                        // rows, and finalize only reads
-                                        // i < M*Kp — an epilogue edit that
-                                        // skips stores must zero-fill first.
-  constexpr int BM = 128;
-  constexpr int PAD = KS / 2;
-  constexpr int RS = KS * KS;
-  constexpr int WM = (BN >= 64) ? 2 : 4;
-  constexpr int WN = 4 / WM;
-  constexpr int FM = BM / WM / 16;  // fragments per wave in M
-  constexpr int FN = BN / WN / 16;  // fragments per wave in N
-  constexpr int SLOTS_B = BN * 4;
-  constexpr int NBS = (SLOTS_B + 255) / 256;  // B slots per thread (1 or 2)
-  constexpr int LB = NBS * 256 * 8;  // B buffer elems (>= SLOTS_B*8, so the
-                                     // glds of invalid slots lands in-pad)
-  const int KG = RS * Cp;
-  const long M = (long)N * H * W;
-
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  // SPLITK uses a 5-deep buffer ring (see below); the 2-phase path uses
-  // 2 stage buffers of DK 32-K steps each (DK=2 for the narrow tiles).
-  constexpr int NBUF = SPLITK ? 5 : ((BN <= 32) ? 4 : 2);
-  bf16_t* lA = reinterpret_cast<bf16_t*>(smem);              // NBUF x BM*32
-  bf16_t* lB = lA + NBUF * BM * 32;                          // NBUF x LB
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int wr = wid / WN;
-  const int wc = wid % WN;
-  const long m0 = (long)blockIdx.x * BM;
-  const int n0 = blockIdx.y * BN;
-
-  // ---- per-thread A-slot geometry (2 slots) ----
-  int aOy[2], aOx[2], aKb[2];
-  long aRowBase[2];  // (n*H) term
-  bool aMv[2];
-  const int HW = H * W;
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    int slot = tid + s * 256;
-    int i = slot & 15, kb = (slot >> 4) & 3;
-    int mf = slot >> 6;
-    long m = m0 + mf * 16 + i;
-    aMv[s] = m < M;
-    long mm = aMv[s] ? m : 0;
-    int n = (int)(mm / HW);
-    int rem = (int)(mm - (long)n * HW);
-    aOy[s] = rem / W;
-    aOx[s] = rem - aOy[s] * W;
-    aRowBase[s] = (long)n * H;
-    aKb[s] = kb;
-  }
-  // ---- per-thread B-slot geometry ----
-  int bK[NBS], bKb[NBS];
-  bool bV[NBS];
-#pragma unroll
-  for (int s = 0; s < NBS; ++s) {
-    int slot = tid + s * 256;
-    bV[s] = slot < SLOTS_B;
-    int j = slot & 15, kb = (slot >> 4) & 3;
-    int nf = (slot >> 6);
-    bK[s] = n0 + nf * 16 + j;
-    bKb[s] = kb;
-  }
-
-  static_assert(WN_MFMA_KMAP == 0, "glds staging assumes KMAP 0");
-
-  // Stage one K-step's A and B tiles straight into LDS buffer `buf` with
-  // global_load_lds (16 B per lane, lane-linear LDS image — guide §5
-  // "common mistake 1": width-16 glds is the staging lever). Out-of-range
-  // lanes (conv halo, channel pad, M tail) read from Zero16 instead —
-  // every lane always issues its DMA so the image is fully defined.
-  auto stage = [&](int buf, int k0) {
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const bf16_t* src = Zero16;
-      int rsc = k0 + aKb[s] * 8;
-      if (aMv[s] && rsc < KG) {
-        int tap = rsc >> log2Cp;
-        int c = rsc & (Cp - 1);
-        int dy = tap / KS, dx = tap - (tap / KS) * KS;
-        int iy = aOy[s] + dy - PAD, ix = aOx[s] + dx - PAD;
-        if (iy >= 0 && iy < H && ix >= 0 && ix < W)
-          src = X + (((aRowBase[s] + iy) * W + ix) << log2Cp) + c;
-      }
-      __builtin_amdgcn_global_load_lds(
-          src, lA + buf * (BM * 32) + (tid + s * 256) * 8, 16, 0, 0);
-    }
-#pragma unroll
-    for (int s = 0; s < NBS; ++s) {
-      const bf16_t* src = Zero16;
-      int rsc = k0 + bKb[s] * 8;
-      if (bV[s] && bK[s] < Kp && rsc < KG)
-        src = Wp + (long)bK[s] * KG + rsc;
-      __builtin_amdgcn_global_load_lds(
-          src, lB + buf * LB + (tid + s * 256) * 8, 16, 0, 0);
-    }
-  };
-
-  f32x4 acc[FM][FN];
-#pragma unroll
-  for (int a = 0; a < FM; ++a)
-#pragma unroll
-    for (int b = 0; b < FN; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int nkAll = (KG + 31) / 32;
-  // SPLITK: z-slice [ks0, nk) of the K loop; else the whole range. Floor
-  // slicing keeps every slice non-empty for gz <= nkAll, so every fp32
-  // slab is fully written (the finalize pass sums all of them).
-  int ks0 = 0, nk = nkAll;
-  if (SPLITK) {
-    ks0 = (int)((long)blockIdx.z * nkAll / gridDim.z);
-    nk = (int)((long)(blockIdx.z + 1) * nkAll / gridDim.z);
-  }
-  const int lg = lane >> 4;   // fragment k-group
-  const int li = lane & 15;   // fragment row/col
-
-  if constexpr (SPLITK) {
-    // Split-K shapes run at ~1 block/CU (small M, chip filled by K
-    // slices): the per-step vmcnt(0) drain is fully exposed there, so use
-    // a 3-buffer glds pipeline with COUNTED vmcnt + raw barriers (guide
-    // §5 "Pipelining across barriers": +40-83% in the 1-block/CU regime;
-    // measured NEGATIVE at the big-M shapes' 5-blocks/CU occupancy, which
-    // keep the simpler 2-phase below).
-    constexpr int GPS = 2 + NBS;  // glds per stage per thread (3 or 4)
-    // wait until at most `tiles`' worth of glds remain outstanding
-    auto wait_tiles = [&](int tiles) {
-      if constexpr (GPS == 3) {
-        switch (tiles) {
-          case 3: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-          case 2: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-          case 1: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-          default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-      } else {
-        switch (tiles) {
-          case 3: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-          case 2: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-          case 1: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-          default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-      }
-    };
-    // prologue: up to 4 tiles in flight, wait for tile ks0 only
-    for (int t = 0; t < 4 && ks0 + t < nk; ++t) stage(t, (ks0 + t) * 32);
-    wait_tiles(min(nk - ks0 - 1, 3));
-    __builtin_amdgcn_s_barrier();
-    for (int ks = ks0; ks < nk; ++ks) {
-      const int b = (ks - ks0) % 5;
-      if (ks + 4 < nk) stage((b + 4) % 5, (ks + 4) * 32);
-      bf16x8 aF[FM], bF[FN];
-#pragma unroll
-      for (int fm = 0; fm < FM; ++fm)
-        aF[fm] = *reinterpret_cast<const bf16x8*>(
-            lA + b * (BM * 32) + (((wr * FM + fm) * 4 + lg) * 16 + li) * 8);
-#pragma unroll
-      for (int fn = 0; fn < FN; ++fn)
-        bF[fn] = *reinterpret_cast<const bf16x8*>(
-            lB + b * LB + (((wc * FN + fn) * 4 + lg) * 16 + li) * 8);
-#pragma unroll
-      for (int fm = 0; fm < FM; ++fm)
-#pragma unroll
-        for (int fn = 0; fn < FN; ++fn)
-          acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              aF[fm], bF[fn], acc[fm][fn], 0, 0, 0);
-      if (ks + 1 < nk) {
-        wait_tiles(min(nk - ks - 2, 3));  // tile ks+1 landed
-        __builtin_amdgcn_s_barrier();
-      }
-    }
-  } else {
-    // 2-phase glds pipeline (guide §5 "minimum 2-phase"): issue next
-    // tile's DMA first, ds_read + MFMA the current buffer, one
-    // vmcnt(0)+barrier per staged tile (the __syncthreads drains the DMA).
-    // Narrow tiles (BN<=32) do only FM*FN<=4 MFMAs per 32-K step, so they
-    // stage DK=2 steps per barrier to amortize it (K tails are zero-filled
-    // by the staging, so no edge code).
-    constexpr int DK = (BN <= 32) ? 2 : 1;
-#pragma unroll
-    for (int h = 0; h < DK; ++h) stage(h, (ks0 + h) * 32);
-    __syncthreads();
-    int cur = 0;
-    const int nk2 = (nk - ks0 + DK - 1) / DK;
-    for (int ks2 = 0; ks2 < nk2; ++ks2) {
-      if (ks2 + 1 < nk2) {
-#pragma unroll
-        for (int h = 0; h < DK; ++h)
-          stage((cur ^ 1) * DK + h, (ks0 + (ks2 + 1) * DK + h) * 32);
-      }
-#pragma unroll
-      for (int h = 0; h < DK; ++h) {
-        bf16x8 aF[FM], bF[FN];
-#pragma unroll
-        for (int fm = 0; fm < FM; ++fm) {
-          int mfG = wr * FM + fm;
-          aF[fm] = *reinterpret_cast<const bf16x8*>(
-              lA + (cur * DK + h) * (BM * 32) +
-              ((mfG * 4 + lg) * 16 + li) * 8);
-        }
-#pragma unroll
-        for (int fn = 0; fn < FN; ++fn) {
-          int nfG = wc * FN + fn;
-          bF[fn] = *reinterpret_cast<const bf16x8*>(
-              lB + (cur * DK + h) * LB + ((nfG * 4 + lg) * 16 + li) * 8);
-        }
-#pragma unroll
-        for (int fm = 0; fm < FM; ++fm)
-#pragma unroll
-          for (int fn = 0; fn < FN; ++fn)
-            acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                aF[fm], bF[fn], acc[fm][fn], 0, 0, 0);
-      }
-      if (ks2 + 1 < nk2) __syncthreads();
-      cur ^= 1;
-    }
-  }
-
-  // ---- epilogue: bias + activation (+ pad-channel zeroing), or fp32
-  //      partial-sum atomics when this launch is a split-K slice ----
-  const int lr4 = (lane >> 4) * 4;
-#pragma unroll
-  for (int fn = 0; fn < FN; ++fn) {
-    const int k = n0 + (wc * FN + fn) * 16 + li;
-    if (k >= Kp) continue;
-    const float bv = (Bias != nullptr && k < Klog) ? Bias[k] : 0.f;
-    const bool kpad = k >= Klog;
-#pragma unroll
-    for (int fm = 0; fm < FM; ++fm) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        long m = m0 + (wr * FM + fm) * 16 + lr4 + r;
-        if (m >= M) continue;
-        if (SPLITK) {
-          // per-slice fp32 slab, plain stores (no atomics — the finalize
-          // pass reduces over gridDim.z slabs)
-          Y32[((long)blockIdx.z * M + m) * Kp + k] = acc[fm][fn][r];
-        } else {
-          float v = acc[fm][fn][r] + bv;
-          if (act == ACT_RELU) v = fmaxf(v, 0.f);
-          else if (act == ACT_SIGMOID) v = 1.f / (1.f + __expf(-v));
-          if (kpad) v = 0.f;
-          Y[m * Kp + k] = f2bf(v);
-        }
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// 8-wave 256xBN phase-split conv igemm for BIG-M shapes (guide §5 T3+T5:
-// wave role diversity + setprio + counted vmcnt; the 4-wave 2-phase kernel
-// above is schedule-bound at ~480 TF on these shapes — PMC r06/r18: ~58%
-// WAIT_ANY with MFMA, TA and HBM all unsaturated).
-//   - 512 threads = 8 waves as 4(M)x2(N); per-wave output 64 x BN/2.
-//   - 3-deep LDS ring, glds staging (GPS=3 per thread per tile), counted
-//     s_waitcnt vmcnt leaves the next tile's DMA in flight across barriers.
-//   - two MFMA phases per K-step with s_setprio(1) around the matrix math.
-// ---------------------------------------------------------------------------
-
-// VAR: 0 = 2 setprio phases / 3-ring (default); 1 = no setprio;
-// 2 = 4 phases; 3 = 4-deep ring (2 tiles in flight). Runtime-selectable
-// via WN_IGEMM8_VAR for within-box A/B (guide §5.4 rule 24).
-// M32: v_mfma_f32_32x32x16_bf16 fragments (half the MFMA instruction
-// count at the higher 32x32 pipe rate; +5.5% proven on the wgrad).
-template <int BN, int KS, int VAR = 0, bool M32 = false>
-__global__ __launch_bounds__(512, 1) void k_conv_igemm8(
-    const bf16_t* __restrict__ X,   // (N, H, W, Cp)
-    const bf16_t* __restrict__ Wp,  // [Kp][RS*Cp]
-    const float* __restrict__ Bias,
-    bf16_t* __restrict__ Y,         // (N, H, W, Kp)
-    int N, int H, int W, int Cp, int log2Cp, int Kp, int Klog, int act,
-    const bf16_t* __restrict__ Zero16) {
-  static_assert(WN_MFMA_KMAP == 0, "glds staging assumes KMAP 0");
-  constexpr int BM = 256;
-  constexpr int PAD = KS / 2;
-  constexpr int RS = KS * KS;
-  constexpr int WMW = 4, WNW = 2;       // wave grid
-  constexpr int FM = BM / WMW / 16;     // 4 fragments in M per wave
-  constexpr int FN = BN / WNW / 16;     // 4 (BN=128) / 2 (BN=64)
-  constexpr int ASLOT = BM * 32 / 8 / 512;   // = 2
-  constexpr int SLOTS_B = BN * 4;
-  constexpr int BSLOT = (SLOTS_B + 511) / 512;  // = 1
-  constexpr int LA = BM * 32;           // A buffer elems
-  constexpr int LB8 = 512 * 8;          // B buffer elems (>= SLOTS_B*8)
-  const int KG = RS * Cp;
-  const long M = (long)N * H * W;
-
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  // the B buffers start after RING A buffers (the launch sizes the
-  // allocation by the same ring depth)
-  constexpr int RING = (VAR == 3) ? 4 : 3;
-  bf16_t* lA = reinterpret_cast<bf16_t*>(smem);   // RING x LA
-  bf16_t* lB = lA + RING * LA;                    // RING x LB8
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int wr = wid >> 1;
-  const int wc = wid & 1;
-  const long m0 = (long)blockIdx.x * BM;
-  const int n0 = blockIdx.y * BN;
-  const int HW = H * W;
-
-  // A slots: the lane-linear LDS image IS the fragment layout, so the
-  // slot->(m row, k offset) decode differs per MFMA shape:
-  //   16x16x32: slot = (mf16, kb, i16) -> m = mf16*16+i16, kOff = kb*8
-  //   32x32x16: slot = (mf32, t, g, i32) -> m = mf32*32+i32,
-  //             kOff = t*16 + g*8  (lane l reads k = (l>>5)*8+e)
-  int aOy[ASLOT], aOx[ASLOT], aKb[ASLOT];
-  long aRowBase[ASLOT];
-  bool aMv[ASLOT];
-#pragma unroll
-  for (int s = 0; s < ASLOT; ++s) {
-    int slot = tid + s * 512;
-    int mrow, koff;
-    if constexpr (M32) {
-      mrow = (slot >> 7) * 32 + (slot & 31);
-      koff = ((slot >> 6) & 1) * 16 + ((slot >> 5) & 1) * 8;
-    } else {
-      mrow = (slot >> 6) * 16 + (slot & 15);
-      koff = ((slot >> 4) & 3) * 8;
-    }
-    long m = m0 + mrow;
-    aMv[s] = m < M;
-    long mm = aMv[s] ? m : 0;
-    int n = (int)(mm / HW);
-    int rem = (int)(mm - (long)n * HW);
-    aOy[s] = rem / W;
-    aOx[s] = rem - aOy[s] * W;
-    aRowBase[s] = (long)n * H;
-    aKb[s] = koff;
-  }
-  int bK[BSLOT], bKb[BSLOT];
-  bool bV[BSLOT];
-#pragma unroll
-  for (int s = 0; s < BSLOT; ++s) {
-    int slot = tid + s * 512;
-    bV[s] = slot < SLOTS_B;
-    int col, koff;
-    if constexpr (M32) {
-      col = (slot >> 7) * 32 + (slot & 31);
-      koff = ((slot >> 6) & 1) * 16 + ((slot >> 5) & 1) * 8;
-    } else {
-      col = (slot >> 6) * 16 + (slot & 15);
-      koff = ((slot >> 4) & 3) * 8;
-    }
-    bK[s] = n0 + col;
-    bKb[s] = koff;
-  }
-
-  auto stage = [&](int buf, int ks) {
-    const int k0 = ks * 32;
-#pragma unroll
-    for (int s = 0; s < ASLOT; ++s) {
-      const bf16_t* src = Zero16;
-      int rsc = k0 + aKb[s];
-      if (aMv[s] && rsc < KG) {
-        int tap = rsc >> log2Cp;
-        int c = rsc & (Cp - 1);
-        int dy = tap / KS, dx = tap - (tap / KS) * KS;
-        int iy = aOy[s] + dy - PAD, ix = aOx[s] + dx - PAD;
-        if (iy >= 0 && iy < H && ix >= 0 && ix < W)
-          src = X + (((aRowBase[s] + iy) * W + ix) << log2Cp) + c;
-      }
-      __builtin_amdgcn_global_load_lds(
-          src, lA + buf * LA + (tid + s * 512) * 8, 16, 0, 0);
-    }
-#pragma unroll
-    for (int s = 0; s < BSLOT; ++s) {
-      const bf16_t* src = Zero16;
-      int rsc = k0 + bKb[s];
-      if (bV[s] && bK[s] < Kp && rsc < KG)
-        src = Wp + (long)bK[s] * KG + rsc;
-      __builtin_amdgcn_global_load_lds(
-          src, lB + buf * LB8 + (tid + s * 512) * 8, 16, 0, 0);
-    }
-  };
-
-  constexpr int FM32 = BM / WMW / 32;       // 2
-  constexpr int FN32 = (BN / WNW) / 32;     // 2 (BN=128) / 1 (BN=64)
-  f32x4 acc[M32 ? 1 : FM][M32 ? 1 : FN];
-  f32x16 acc32[M32 ? FM32 : 1][M32 ? FN32 : 1];
-#pragma unroll
-  for (int a = 0; a < (M32 ? FM32 : FM); ++a)
-#pragma unroll
-    for (int b = 0; b < (M32 ? FN32 : FN); ++b) {
-      if constexpr (M32) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc32[a][b][e] = 0.f;
-      } else {
-        acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-    }
-
-  const int nk = (KG + 31) / 32;
-  const int lg = lane >> 4, li = lane & 15;
-  constexpr int GPS = ASLOT + BSLOT;  // 3 glds per thread per stage
-  constexpr int AHEAD = RING - 2;  // tiles left in flight at the wait
-  constexpr bool PRIO = (VAR != 1);
-  constexpr int NPH = (VAR == 2) ? 4 : 2;  // M-fragment phases per K-step
-
-  auto wait_tiles = [&](int inflight) {
-    if (inflight >= 2 && AHEAD == 2)
-      asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if (inflight >= 1)
-      asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  };
-  static_assert(GPS == 3, "vmcnt immediates assume 3 glds per stage");
-
-  for (int t = 0; t < RING - 1 && t < nk; ++t) stage(t, t);
-  wait_tiles(min(nk - 1, RING - 2));
-  __builtin_amdgcn_s_barrier();
-
-  for (int ks = 0; ks < nk; ++ks) {
-    const int b = ks % RING;
-    if (ks + RING - 1 < nk) stage((b + RING - 1) % RING, ks + RING - 1);
-    if constexpr (M32) {
-      // lane-linear fragment reads: block (mf32*2+t)*2+g at lane*16B
-      bf16x8 aF[FM32][2], bF[FN32][2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int fn = 0; fn < FN32; ++fn)
-          bF[fn][t] = *reinterpret_cast<const bf16x8*>(
-              lB + b * LB8 + ((wc * FN32 + fn) * 2 + t) * 512 + lane * 8);
-#pragma unroll
-      for (int ph = 0; ph < 2; ++ph) {  // one M fragment per phase
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-          aF[ph][t] = *reinterpret_cast<const bf16x8*>(
-              lA + b * LA + ((wr * FM32 + ph) * 2 + t) * 512 + lane * 8);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int fn = 0; fn < FN32; ++fn)
-            acc32[ph][fn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                aF[ph][t], bF[fn][t], acc32[ph][fn], 0, 0, 0);
-        if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
-      }
-    } else {
-      bf16x8 aF[FM], bF[FN];
-#pragma unroll
-      for (int fn = 0; fn < FN; ++fn)
-        bF[fn] = *reinterpret_cast<const bf16x8*>(
-            lB + b * LB8 + (((wc * FN + fn) * 4 + lg) * 16 + li) * 8);
-#pragma unroll
-      for (int ph = 0; ph < NPH; ++ph) {
-        constexpr int FPP = M32 ? 1 : FM / NPH;  // fragments per phase
-#pragma unroll
-        for (int fm = ph * FPP; fm < (ph + 1) * FPP; ++fm)
-          aF[fm] = *reinterpret_cast<const bf16x8*>(
-              lA + b * LA + (((wr * FM + fm) * 4 + lg) * 16 + li) * 8);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int fm = ph * FPP; fm < (ph + 1) * FPP; ++fm)
-#pragma unroll
-          for (int fn = 0; fn < FN; ++fn)
-            acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                aF[fm], bF[fn], acc[fm][fn], 0, 0, 0);
-        if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
-      }
-    }
-    if (ks + 1 < nk) {
-      wait_tiles(min(nk - ks - 2, AHEAD));
-      __builtin_amdgcn_s_barrier();
-    }
-  }
-
-  if constexpr (M32) {
-    // 32x32 D map: col = lane&31 (k-out), row = (r&3)+8*(r>>2)+4*(lane>>5)
-#pragma unroll
-    for (int fn = 0; fn < FN32; ++fn) {
-      const int k = n0 + (wc * FN32 + fn) * 32 + (lane & 31);
-      if (k >= Kp) continue;
-      const float bv = (Bias != nullptr && k < Klog) ? Bias[k] : 0.f;
-      const bool kpad = k >= Klog;
-#pragma unroll
-      for (int fm = 0; fm < FM32; ++fm) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-          long m = m0 + (wr * FM32 + fm) * 32 + row;
-          if (m >= M) continue;
-          float v = acc32[fm][fn][r] + bv;
-          if (act == ACT_RELU) v = fmaxf(v, 0.f);
-          else if (act == ACT_SIGMOID) v = 1.f / (1.f + __expf(-v));
-          if (kpad) v = 0.f;
-          Y[m * Kp + k] = f2bf(v);
-        }
-      }
-    }
-    return;
-  }
-  // epilogue: bias + activation + pad zeroing
-  const int lr4 = lg * 4;
-#pragma unroll
-  for (int fn = 0; fn < FN; ++fn) {
-    const int k = n0 + (wc * FN + fn) * 16 + li;
-    if (k >= Kp) continue;
-    const float bv = (Bias != nullptr && k < Klog) ? Bias[k] : 0.f;
-    const bool kpad = k >= Klog;
-#pragma unroll
-    for (int fm = 0; fm < FM; ++fm) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        long m = m0 + (wr * FM + fm) * 16 + lr4 + r;
-        if (m >= M) continue;
-        float v = acc[fm][fn][r] + bv;
-        if (act == ACT_RELU) v = fmaxf(v, 0.f);
-        else if (act == ACT_SIGMOID) v = 1.f / (1.f + __expf(-v));
-        if (kpad) v = 0.f;
-        Y[m * Kp + k] = f2bf(v);
-      }
-    }
-  }
-}
-
-// Split-K finalize: Y = act(sum over gz slabs of Y32 + bias), pad zeroed.
-// GZ is a template constant so all slab loads issue in parallel (the
-// runtime-bounded loop serialized up to 8 dependent ~500-cycle loads per
-// element — measured 9.5 us per call, ~1.5 us unrolled).
-template <int GZ>
-__global__ void k_splitk_finalize(const float* __restrict__ Y32,
-                                  const float* __restrict__ Bias,
-                                  bf16_t* __restrict__ Y, long M, int Kp,
-                                  int Klog, int act) {
-  const long total = M * Kp;
-  for (long i0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-       i0 < total; i0 += (long)gridDim.x * blockDim.x * 4) {
-    f32x4 vz[GZ];
-#pragma unroll
-    for (int z = 0; z < GZ; ++z)
-      vz[z] = *reinterpret_cast<const f32x4*>(Y32 + z * total + i0);
-    f32x4 v = vz[0];
-#pragma unroll
-    for (int z = 1; z < GZ; ++z)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] += vz[z][e];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const long i = i0 + e;
-      const int k = (int)(i % Kp);
-      float w = v[e] + ((Bias != nullptr && k < Klog) ? Bias[k] : 0.f);
-      if (act == ACT_RELU) w = fmaxf(w, 0.f);
-      else if (act == ACT_SIGMOID) w = 1.f / (1.f + __expf(-w));
-      if (k >= Klog) w = 0.f;
-      Y[i] = f2bf(w);
-    }
-  }
-}
+#include "conv_common.h"
 
 // ---------------------------------------------------------------------------
 // Weight gradient: dW[k][rsc] = sum_m dY[m][k] * X[m][rsc]
@@ -690,6 +95,30 @@ WN_DEVFN bf16x4 ds_tr16(unsigned addr) {
   return v;
 }
 
+// k_conv_wgrad tile geometry: BK x 128 output tile, m-chunks of CH.
+template <int BK, int CH>
+struct WgradGeo {
+  static constexpr int BR = 128;  // rsc tile
+  // per-chunk tr image kblk stride: CH/4 mblks x 96 elems + 16 pad, which
+  // keeps the stride 8 mod 32 dwords (conflict-free staging writes)
+  static constexpr int KBS = CH / 4 * TR_MBS + 16;  // = TR_KBS at CH=64
+  static constexpr int WR = (BK >= 64) ? 2 : 1;     // wave rows (k dim)
+  static constexpr int WC = 4 / WR;                 // wave cols (rsc dim)
+  static constexpr int FK = BK / WR / 16;  // k fragments per wave
+  static constexpr int FR = BR / WC / 16;  // rsc fragments per wave
+  // M32: the wave tile stays 64x64 (BK>=64), FK32 x FR32 accumulators
+  static constexpr int FK32 = (BK >= 64) ? BK / WR / 32 : 1;
+  static constexpr int FR32 = BR / WC / 32;
+  static constexpr int CPK = KBS / 8;         // 16 B chunks per kblk
+  static constexpr int AC = (BK / 16) * CPK;  // A image chunks
+  static constexpr int BC = (BR / 16) * CPK;  // B image chunks
+  static constexpr int SA = (AC + 255) / 256, SB = (BC + 255) / 256;
+  static constexpr int ABUF = SA * 256 * 8;  // elems per buffer (padded so
+  static constexpr int BBUF = SB * 256 * 8;  //  out-of-image slots land in-pad)
+  static constexpr int LDS_BYTES =
+      2 * (ABUF + BBUF) * (int)sizeof(bf16_t);  // double-buffered
+};
+
 template <int KS, int BK, int CH = 64, bool M32 = false>
 __global__ __launch_bounds__(256, 2) void k_conv_wgrad(
     const bf16_t* __restrict__ dY,  // (N,H,W,Kp)
@@ -699,16 +128,12 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad(
     int splitm, unsigned long long mulHW, unsigned long long mulW,
     const bf16_t* __restrict__ Zero16w) {
   static_assert(WN_MFMA_KMAP == 0, "wgrad staging assumes KMAP 0");
+  using G = WgradGeo<BK, CH>;
   constexpr int PAD = KS / 2;
   constexpr int RS = KS * KS;
-  constexpr int BR = 128;           // rsc tile
-  // per-chunk tr image kblk stride: CH/4 mblks x 96 elems + 16 pad, which
-  // keeps the stride 8 mod 32 dwords (conflict-free staging writes)
-  constexpr int KBS = CH / 4 * TR_MBS + 16;  // = TR_KBS at CH=64
-  constexpr int WR = (BK >= 64) ? 2 : 1;   // wave rows (k dim)
-  constexpr int WC = 4 / WR;               // wave cols (rsc dim)
-  constexpr int FK = BK / WR / 16;  // k fragments per wave
-  constexpr int FR = BR / WC / 16;  // rsc fragments per wave
+  constexpr int BR = G::BR, KBS = G::KBS, WR = G::WR, WC = G::WC;
+  constexpr int FK = G::FK, FR = G::FR, CPK = G::CPK, AC = G::AC, BC = G::BC;
+  constexpr int SA = G::SA, SB = G::SB, ABUF = G::ABUF, BBUF = G::BBUF;
   const int KG = RS * Cp;
   const long M = (long)N * H * W;
   const int HW = H * W;
@@ -720,14 +145,6 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad(
   // SOURCE gathers the right 16 B of dY/X (pad/halo lanes read Zero16).
   // Double-buffered: the next chunk's DMA issues before this chunk's
   // MFMAs and drains at the single trailing barrier.
-  constexpr int CPK = KBS / 8;               // chunks per kblk
-  constexpr int AC = (BK / 16) * CPK;        // A image chunks
-  constexpr int BC = (BR / 16) * CPK;        // B image chunks
-  constexpr int SA = (AC + 255) / 256;
-  constexpr int SB = (BC + 255) / 256;
-  constexpr int ABUF = SA * 256 * 8;         // elems per buffer (padded so
-  constexpr int BBUF = SB * 256 * 8;         //  out-of-image slots land in-pad)
-
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* lA = reinterpret_cast<bf16_t*>(smem);   // 2 x ABUF
   bf16_t* lB = lA + 2 * ABUF;                     // 2 x BBUF
@@ -799,8 +216,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad(
   // count for the same MACs at the 2382-vs-2075 TF pipe rate (PMC shows
   // the 16x16 wgrad is MFMA-pipe-saturated). Wave tile stays 64x64
   // (BK>=64): FK32 x FR32 accumulators of 16 f32.
-  constexpr int FK32 = (BK >= 64) ? BK / WR / 32 : 1;
-  constexpr int FR32 = BR / WC / 32;
+  constexpr int FK32 = G::FK32, FR32 = G::FR32;
   f32x4 acc[M32 ? 1 : FK][M32 ? 1 : FR];
   f32x16 acc32[M32 ? FK32 : 1][M32 ? FR32 : 1];
 #pragma unroll
@@ -1071,6 +487,25 @@ constexpr bool pt_tr_conflict_free(int COLS, int maxShift) {
 }
 
 template <int KS, int BK, int CT, int CH>
+struct PatchGeo {
+  static constexpr int WR = BK / 32, WC = CT / 32;  // wave grid over the tile
+  static constexpr int WK = 4 / (WR * WC);  // waves interleaving k-steps
+  static constexpr int KST = CH / 16;       // k-steps per chunk
+  static constexpr int KSTW = KST / WK;     // k-steps per wave
+  static constexpr int NPX = CH + KS - 1;   // patch pixels (2*PAD halo)
+  static constexpr int ACPR = BK / 8, BCPR = CT / 8;  // 16 B chunks per row
+  static constexpr int ASLOTS = CH * ACPR, BSLOTS = NPX * BCPR;
+  static constexpr int SA = (ASLOTS + 255) / 256, SB = (BSLOTS + 255) / 256;
+  static constexpr int ABYTES = SA * 256 * 16;  // padded: surplus slots stay
+  static constexpr int BBYTES = SB * 256 * 16;  // inside
+  static constexpr int SLABN = WR * 8 * CT * KS;  // floats per slab copy
+  // staging double buffer, reused by the epilogue's WK slab copies
+  static constexpr int LDS_BYTES =
+      2 * (ABYTES + BBYTES) > WK * SLABN * 4 ? 2 * (ABYTES + BBYTES)
+                                             : WK * SLABN * 4;
+};
+
+template <int KS, int BK, int CT, int CH>
 __global__ __launch_bounds__(256, 2) void k_conv_wgrad_patch(
     const bf16_t* __restrict__ dY,  // (N,H,W,Kp)
     const bf16_t* __restrict__ X,   // (N,H,W,Cp)
@@ -1079,18 +514,14 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_patch(
     const bf16_t* __restrict__ Zero16w) {
   static_assert(WN_MFMA_KMAP == 0, "wgrad staging assumes KMAP 0");
   static_assert((BK == 32 || BK == 64) && (CT == 32 || CT == 64));
+  using G = PatchGeo<KS, BK, CT, CH>;
   constexpr int PAD = KS / 2;
-  constexpr int WR = BK / 32, WC = CT / 32;  // wave grid over the tile
-  constexpr int WK = 4 / (WR * WC);          // waves interleaving k-steps
-  constexpr int KST = CH / 16;               // k-steps per chunk
+  constexpr int WR = G::WR, WC = G::WC, WK = G::WK, KST = G::KST;
   static_assert(CH % 16 == 0 && KST % WK == 0);
-  constexpr int KSTW = KST / WK;             // k-steps per wave
-  constexpr int NPX = CH + KS - 1;           // patch pixels (2*PAD halo)
-  constexpr int ACPR = BK / 8, BCPR = CT / 8;  // 16 B chunks per row
-  constexpr int ASLOTS = CH * ACPR, BSLOTS = NPX * BCPR;
-  constexpr int SA = (ASLOTS + 255) / 256, SB = (BSLOTS + 255) / 256;
-  constexpr int ABYTES = SA * 256 * 16;  // padded: surplus slots stay inside
-  constexpr int BBYTES = SB * 256 * 16;
+  constexpr int KSTW = G::KSTW, NPX = G::NPX;
+  constexpr int ASLOTS = G::ASLOTS, BSLOTS = G::BSLOTS;
+  constexpr int SA = G::SA, SB = G::SB;
+  constexpr int ABYTES = G::ABYTES, BBYTES = G::BBYTES;
   static_assert(pt_image_linear(CH, BK) && pt_image_linear(NPX, CT),
                 "glds slot order != image chunk order");
   static_assert(pt_tr_conflict_free(BK, 12) &&
@@ -1256,9 +687,9 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_patch(
   //      LDS in 4 slabs of WR*8 k rows laid out [k][c][dx] — dW's own order
   //      for one dy — the WK k-step waves' partial sums are added on the
   //      way out, and consecutive lanes add to consecutive addresses. ----
-  constexpr int SLABN = WR * 8 * CT * KS;  // floats per slab copy
-  // all WK slab copies: 4096*KS bytes; the host sizes LDS to the larger of
-  // this and the staging buffers
+  constexpr int SLABN = G::SLABN;  // floats per slab copy
+  // all WK slab copies: 4096*KS bytes; LDS_BYTES is the larger of this and
+  // the staging buffers
   static_assert(WK * SLABN * 4 == 4096 * KS);
   float* slab = reinterpret_cast<float*>(smem);
   __syncthreads();  // every wave is past its last tr read; no DMA in flight
@@ -1344,7 +775,7 @@ struct Patch16Geo {
   static constexpr int SB = ((PXA + KS) * BCPR + 255) / 256;
   static constexpr int ABYTES = SA * 256 * 16, BBYTES = SB * 256 * 16;
   static constexpr int SLABN = WR * 8 * 16 * KS;  // floats per slab copy
-  static constexpr int LDS =
+  static constexpr int LDS_BYTES =
       2 * (ABYTES + BBYTES) > WK * SLABN * 4 ? 2 * (ABYTES + BBYTES)
                                              : WK * SLABN * 4;
 };
@@ -1786,266 +1217,11 @@ __global__ void k_bias_grad_reduce(const float* __restrict__ Part,
   }
   if (threadIdx.x == 0) dB[k] += red[0];
 }
-
-// ---------------------------------------------------------------------------
-// Weight packing: NCHW fp32 master -> bf16 k-major [Kp][RS*Cp] (fwd) and
-// c-major rotated [Cp][RS*Kp] (dgrad).
-// ---------------------------------------------------------------------------
-
-__global__ void k_pack_fwd(const float* __restrict__ Wm,  // (K,C,R,S)
-                           bf16_t* __restrict__ out,      // [Kp][RS*Cp]
-                           int K, int C, int R, int S, int Kp, int Cp) {
-  const int KG = R * S * Cp;
-  const long total = (long)Kp * KG;
-  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-       idx += (long)gridDim.x * blockDim.x) {
-    int k = (int)(idx / KG);
-    int rsc = (int)(idx - (long)k * KG);
-    int tap = rsc / Cp, c = rsc - (rsc / Cp) * Cp;
-    int r = tap / S, s = tap - (tap / S) * S;
-    float v = (k < K && c < C) ? Wm[(((long)k * C + c) * R + r) * S + s] : 0.f;
-    out[idx] = f2bf(v);
-  }
-}
-
-__global__ void k_pack_dgrad(const float* __restrict__ Wm,  // (K,C,R,S)
-                             bf16_t* __restrict__ out,      // [Cp][RS*Kp]
-                             int K, int C, int R, int S, int Kp, int Cp) {
-  const int KG = R * S * Kp;
-  const long total = (long)Cp * KG;
-  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-       idx += (long)gridDim.x * blockDim.x) {
-    int c = (int)(idx / KG);
-    int rsk = (int)(idx - (long)c * KG);
-    int tap = rsk / Kp, k = rsk - (rsk / Kp) * Kp;
-    int rr = tap / S, ss = tap - (tap / S) * S;
-    int r = R - 1 - rr, s = S - 1 - ss;  // rotate 180
-    float v = (c < C && k < K) ? Wm[(((long)k * C + c) * R + r) * S + s] : 0.f;
-    out[idx] = f2bf(v);
-  }
-}
-
-// Batched repack: one launch packs EVERY layer's fwd + dgrad layouts from
-// the fp32 masters (the per-layer k_pack_* launches cost ~5 us each x 36
-// per training step under the lazy per-ConvSpec refresh). desc: int64
-// [njobs][9] = (Wm, wp, wd, K, C, R, S, Kp, Cp).
-__global__ void k_pack_all(const long* __restrict__ desc, int njobs) {
-  const long tid0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long nthreads = (long)gridDim.x * blockDim.x;
-  for (int j = 0; j < njobs; ++j) {
-    const long* d = desc + (long)j * 9;
-    const float* Wm = reinterpret_cast<const float*>(d[0]);
-    bf16_t* wp = reinterpret_cast<bf16_t*>(d[1]);
-    bf16_t* wd = reinterpret_cast<bf16_t*>(d[2]);
-    const int K = (int)d[3], C = (int)d[4], R = (int)d[5], S = (int)d[6];
-    const int Kp = (int)d[7], Cp = (int)d[8];
-    const int KGf = R * S * Cp;
-    const long tf = (long)Kp * KGf;
-    for (long idx = tid0; idx < tf; idx += nthreads) {
-      int k = (int)(idx / KGf);
-      int rsc = (int)(idx - (long)k * KGf);
-      int tap = rsc / Cp, c = rsc - (rsc / Cp) * Cp;
-      int r = tap / S, ss = tap - (tap / S) * S;
-      float v =
-          (k < K && c < C) ? Wm[(((long)k * C + c) * R + r) * S + ss] : 0.f;
-      wp[idx] = f2bf(v);
-    }
-    const int KGd = R * S * Kp;
-    const long td = (long)Cp * KGd;
-    for (long idx = tid0; idx < td; idx += nthreads) {
-      int c = (int)(idx / KGd);
-      int rsk = (int)(idx - (long)c * KGd);
-      int tap = rsk / Kp, k = rsk - (rsk / Kp) * Kp;
-      int rr = tap / S, sss = tap - (tap / S) * S;
-      int r = R - 1 - rr, s2 = S - 1 - sss;  // rotate 180
-      float v =
-          (c < C && k < K) ? Wm[(((long)k * C + c) * R + r) * S + s2] : 0.f;
-      wd[idx] = f2bf(v);
-    }
-  }
-}
-
-void pack_all(const at::Tensor& desc, int64_t njobs) {
-  TORCH_CHECK(desc.is_cuda() && desc.dtype() == at::kLong &&
-              desc.is_contiguous());
-  hipStream_t stream = at::cuda::getCurrentHIPStream();
-  hipLaunchKernelGGL(k_pack_all, dim3(512), dim3(256), 0, stream,
-                     desc.data_ptr<long>(), (int)njobs);
-  HIP_CHECK_LAST();
-}
-
 // ---------------------------------------------------------------------------
 // Host-side dispatch
 // ---------------------------------------------------------------------------
 
 namespace {
-
-inline int log2i(int v) {
-  int l = 0;
-  while ((1 << l) < v) ++l;
-  TORCH_CHECK((1 << l) == v, "value not a power of two: ", v);
-  return l;
-}
-
-// Which forward kernel a conv shape runs on, and on what grid. The single
-// source of the dispatch rule: launch_conv_bn launches what this returns and
-// conv2d_fwd_plan reports it to the tests.
-enum ConvTier { TIER_IGEMM = 0, TIER_SPLITK = 1, TIER_IGEMM8 = 2 };
-
-struct ConvPlan {
-  ConvTier tier;
-  int BN;      // N tile: 16 / 32 / 64 / 128
-  int gx, gy;  // 128-row M blocks, BN-wide N blocks
-  int nk;      // 32-wide K tiles
-  int gz;      // split-K slices (1 unless tier == TIER_SPLITK)
-};
-
-inline ConvPlan conv_plan(long M, int Cp, int Kp, int ks) {
-  ConvPlan p;
-  p.BN = Kp >= 128 ? 128 : Kp == 64 ? 64 : Kp == 32 ? 32 : 16;
-  p.gx = (int)((M + 127) / 128);
-  p.gy = (Kp + p.BN - 1) / p.BN;
-  p.nk = (ks * ks * Cp + 31) / 32;
-  // Small-M shapes (e.g. VGG 14^2/7^2 layers at bs=16) leave most of the
-  // 256 CUs idle; split the K loop across gz slices into fp32 partials,
-  // then finalize bias+act+bf16 in a second tiny pass.
-  const int base = p.gx * p.gy;
-  int gz = 1;
-  if (base < 320 && p.nk >= 16)
-    gz = std::min(std::max(1, 512 / base), p.nk / 4);
-  // finalize's unrolled reads tolerate more slabs for the tiniest
-  // (grid-limited) shapes; snap >8 to the instantiated 12/16 variants
-  gz = std::min(gz, base < 64 ? 16 : 8);
-  if (gz > 8) gz = (gz >= 16) ? 16 : 12;
-  p.gz = gz;
-  p.tier = TIER_IGEMM;
-  if (gz > 1) {
-    p.tier = TIER_SPLITK;
-  } else if (p.BN >= 64) {
-    static const long m8_thresh = [] {
-      // A/B override: the M threshold above which the 8-wave 256-row
-      // igemm8 is used instead of the 4-wave 128-row igemm
-      const char* e = getenv("WN_IGEMM8_MTHRESH");
-      return e ? atol(e) : 16384L;
-    }();
-    if (M >= m8_thresh) p.tier = TIER_IGEMM8;
-  }
-  return p;
-}
-
-template <int KS>
-void launch_conv_bn(const at::Tensor& x, const at::Tensor& wp,
-                    const c10::optional<at::Tensor>& bias, at::Tensor& y,
-                    int Klog, int act, hipStream_t stream) {
-  const int N = x.size(0), H = x.size(1), W = x.size(2), Cp = x.size(3);
-  const int Kp = y.size(3);
-  const long M = (long)N * H * W;
-  const float* bptr =
-      bias.has_value() ? bias->data_ptr<float>() : nullptr;
-  const ConvPlan plan = conv_plan(M, Cp, Kp, KS);
-  const int gx = plan.gx, gy = plan.gy, gz = plan.gz;
-  // 16 B zero source for glds halo/pad lanes (per-device, created once)
-  static thread_local at::Tensor zero16;
-  if (!zero16.defined() || zero16.device() != x.device())
-    zero16 = at::zeros({8}, x.options());
-  const bf16_t* zptr = (const bf16_t*)zero16.data_ptr();
-
-  auto launch = [&](auto bn_const) {
-    constexpr int BN = decltype(bn_const)::value;
-    constexpr int NBS = (BN * 4 + 255) / 256;
-    constexpr int DKH = (BN <= 32) ? 2 : 1;
-    const size_t lds =
-        (2 * DKH * 128 * 32 + 2 * DKH * NBS * 256 * 8) * sizeof(bf16_t);
-    if (plan.tier == TIER_SPLITK) {
-      auto y32 = at::empty({gz, M, (long)Kp}, x.options().dtype(at::kFloat));
-      const size_t lds5 =
-          (5 * 128 * 32 + 5 * NBS * 256 * 8) * sizeof(bf16_t);
-      hipLaunchKernelGGL((k_conv_igemm<BN, KS, true>), dim3(gx, gy, gz),
-                         dim3(256), lds5, stream,
-                         (const bf16_t*)x.data_ptr(),
-                         (const bf16_t*)wp.data_ptr(), bptr,
-                         (bf16_t*)y.data_ptr(), N, H, W, Cp, log2i(Cp), Kp,
-                         Klog, act, zptr, y32.data_ptr<float>());
-      const long total = M * Kp;
-      const int fb = (int)std::min<long>(512, (total / 4 + 255) / 256);
-      auto fin = [&](auto gz_const) {
-        constexpr int GZ = decltype(gz_const)::value;
-        hipLaunchKernelGGL((k_splitk_finalize<GZ>), dim3(fb), dim3(256), 0,
-                           stream, y32.data_ptr<float>(), bptr,
-                           (bf16_t*)y.data_ptr(), M, Kp, Klog, act);
-      };
-      switch (gz) {
-        case 2: fin(std::integral_constant<int, 2>{}); break;
-        case 3: fin(std::integral_constant<int, 3>{}); break;
-        case 4: fin(std::integral_constant<int, 4>{}); break;
-        case 5: fin(std::integral_constant<int, 5>{}); break;
-        case 6: fin(std::integral_constant<int, 6>{}); break;
-        case 7: fin(std::integral_constant<int, 7>{}); break;
-        case 12: fin(std::integral_constant<int, 12>{}); break;
-        case 16: fin(std::integral_constant<int, 16>{}); break;
-        default: fin(std::integral_constant<int, 8>{}); break;
-      }
-    } else {
-      bool done8 = false;
-      if constexpr (BN >= 64) {
-        if (plan.tier == TIER_IGEMM8) {  // big-M: 8-wave 256-row phase-split
-          static const int var = [] {
-            const char* e = getenv("WN_IGEMM8_VAR");
-            return e ? atoi(e) : 0;
-          }();
-          static const bool m32 = [] {
-            const char* e = getenv("WN_IGEMM8_M32");
-            // default OFF: A/B measured a tie on training and -10% at
-            // bs=1 1080p inference (the wgrad M32, by contrast, is +5.5%)
-            return e != nullptr && atoi(e) != 0;
-          }();
-          const int gx8 = (int)((M + 255) / 256);
-          const int ring = (var == 3) ? 4 : 3;
-          const size_t lds8 =
-              (size_t)(ring * 256 * 32 + ring * 512 * 8) * sizeof(bf16_t);
-          auto l8 = [&](auto var_const) {
-            constexpr int V = decltype(var_const)::value;
-            hipLaunchKernelGGL((k_conv_igemm8<BN, KS, V>), dim3(gx8, gy),
-                               dim3(512), lds8, stream,
-                               (const bf16_t*)x.data_ptr(),
-                               (const bf16_t*)wp.data_ptr(), bptr,
-                               (bf16_t*)y.data_ptr(), N, H, W, Cp,
-                               log2i(Cp), Kp, Klog, act, zptr);
-          };
-          if (m32) {
-            hipLaunchKernelGGL((k_conv_igemm8<BN, KS, 0, true>),
-                               dim3(gx8, gy), dim3(512), lds8, stream,
-                               (const bf16_t*)x.data_ptr(),
-                               (const bf16_t*)wp.data_ptr(), bptr,
-                               (bf16_t*)y.data_ptr(), N, H, W, Cp,
-                               log2i(Cp), Kp, Klog, act, zptr);
-          } else {
-            switch (var) {
-              case 1: l8(std::integral_constant<int, 1>{}); break;
-              case 2: l8(std::integral_constant<int, 2>{}); break;
-              case 3: l8(std::integral_constant<int, 3>{}); break;
-              default: l8(std::integral_constant<int, 0>{});
-            }
-          }
-          done8 = true;
-        }
-      }
-      if (!done8)
-        hipLaunchKernelGGL((k_conv_igemm<BN, KS>), dim3(gx, gy), dim3(256),
-                           lds, stream, (const bf16_t*)x.data_ptr(),
-                           (const bf16_t*)wp.data_ptr(), bptr,
-                           (bf16_t*)y.data_ptr(), N, H, W, Cp, log2i(Cp),
-                           Kp, Klog, act, zptr);
-    }
-  };
-  switch (plan.BN) {
-    case 128: launch(std::integral_constant<int, 128>{}); break;
-    case 64: launch(std::integral_constant<int, 64>{}); break;
-    case 32: launch(std::integral_constant<int, 32>{}); break;
-    default: launch(std::integral_constant<int, 16>{});
-  }
-  HIP_CHECK_LAST();
-}
 
 // k_wgrad_smallk launch shape: blocks over (tap, m-slice) and rows in flight
 // per thread (sweep: docs/KERNELS.md, small-K section).
@@ -2057,45 +1233,37 @@ constexpr int WGRAD_SMALLK_U = 4;
 constexpr double WGRAD_PATCH16_BLOCKS_K = 80.0;
 constexpr int WGRAD_PATCH16_BLOCKS_MAX = 1024;
 
-// (KS, Cp, Kp) classes where k_conv_wgrad_patch measured faster than
-// k_conv_wgrad on MI355X (table: docs/KERNELS.md, wgrad section).
-inline bool wgrad_patch_wins(int ks, int Cp, int Kp) {
-  // every instantiated class measured faster, the Cp = 16 tap-pair classes
-  // (k7 16->128, k7 16->32, k5 16->64, k3 16->128) included
-  (void)ks; (void)Cp; (void)Kp;
-  return true;
+// Split-m block count of the patch kernels. Their time is main loop +
+// epilogue atomics: T(blocks) ~ a*work/blocks + b*blocks*tile, with work =
+// gx*gy*chunks*k-steps and tile = atomics per block, so the optimum is
+// blocks ~ k * sqrt(work/tile), up to `cap` (beyond ~3 resident blocks per CU
+// more blocks only add atomics). k and cap are fitted per kernel to block
+// sweeps at 112^2 and 256^2 (docs/KERNELS.md). WN_WGRAD_PATCH_BLOCKS
+// overrides the count for A/B sweeps. Returns gridDim.z.
+inline int patch_split(double work, int tile, int gxgy, double k, int cap,
+                       long maxChunks) {
+  int blocks = std::min((int)(k * std::sqrt(work / tile)), cap);
+  if (const char* be = getenv("WN_WGRAD_PATCH_BLOCKS")) blocks = atoi(be);
+  const int split = std::max(1, (blocks + gxgy / 2) / gxgy);
+  return (int)std::min<long>(split, maxChunks);
 }
 
 template <int KS, int BKCT, int CH>
 void launch_wgrad_patch_t(const at::Tensor& dy, const at::Tensor& x,
                           at::Tensor& dw, const bf16_t* zero16,
                           hipStream_t stream) {
+  using G = PatchGeo<KS, BKCT, BKCT, CH>;
   const int N = x.size(0), H = x.size(1), W = x.size(2), Cp = x.size(3);
   const int Kp = dy.size(3);
   const int K = dw.size(0), C = dw.size(1);
   const int nSeg = (W + CH - 1) / CH;
   const int gx = Kp / BKCT, gy = (Cp / BKCT) * KS;
-  // Split-m block count. The kernel's time is main loop + epilogue
-  // atomics: T(blocks) ~ a*work/blocks + b*blocks*tile, with work =
-  // gx*gy*chunks*k-steps and tile = BK*CT*KS atomics per block, so the
-  // optimum is blocks ~ sqrt(work/tile). The constant is fitted to block
-  // sweeps at 112^2 and 256^2 (docs/KERNELS.md); beyond ~3 resident blocks
-  // per CU more blocks only add atomics. WN_WGRAD_PATCH_BLOCKS overrides
-  // the count for A/B sweeps.
   const double work = (double)gx * gy * N * H * nSeg * (CH / 16);
-  int blocks = (int)(110.0 * std::sqrt(work / (BKCT * BKCT * KS)));
-  blocks = std::min(blocks, 768);
-  if (const char* be = getenv("WN_WGRAD_PATCH_BLOCKS")) blocks = atoi(be);
-  int split = std::max(1, (blocks + gx * gy / 2) / (gx * gy));
-  split = (int)std::min<long>(split, (long)N * H * nSeg);
-  constexpr int SA = (CH * (BKCT / 8) + 255) / 256;
-  constexpr int SB = ((CH + KS - 1) * (BKCT / 8) + 255) / 256;
-  // staging double buffer, reused by the epilogue's 4096*KS-byte slab
-  const size_t lds =
-      std::max<size_t>((size_t)2 * (SA + SB) * 256 * 16, (size_t)4096 * KS);
+  const int split = patch_split(work, BKCT * BKCT * KS, gx * gy, 110.0, 768,
+                                (long)N * H * nSeg);
   hipLaunchKernelGGL((k_conv_wgrad_patch<KS, BKCT, BKCT, CH>),
-                     dim3(gx, gy, split), dim3(256), lds, stream,
-                     (const bf16_t*)dy.data_ptr(),
+                     dim3(gx, gy, split), dim3(256), (size_t)G::LDS_BYTES,
+                     stream, (const bf16_t*)dy.data_ptr(),
                      (const bf16_t*)x.data_ptr(), dw.data_ptr<float>(), N, H,
                      W, Cp, Kp, K, C, nSeg, zero16);
 }
@@ -2110,23 +1278,19 @@ void launch_wgrad_patch16_t(const at::Tensor& dy, const at::Tensor& x,
   const int K = dw.size(0), C = dw.size(1);
   const int nSeg = (W + CH - 1) / CH;
   const int gx = Kp / BK, gy = KS;
-  // same sqrt(work/tile) rule as launch_wgrad_patch_t; the tile (BK*16*KS
-  // atomics) is 4x smaller than 64x64, so more blocks pay. Constant and cap
-  // fitted to WN_WGRAD_PATCH_BLOCKS sweeps at 112^2 and 256^2
-  // (docs/KERNELS.md).
+  // the tile (BK*16*KS atomics) is 4x smaller than 64x64, so more blocks pay
   const double work = (double)gx * gy * N * H * nSeg * (CH / 16);
-  int blocks = (int)(WGRAD_PATCH16_BLOCKS_K * std::sqrt(work / (BK * 16 * KS)));
-  blocks = std::min(blocks, WGRAD_PATCH16_BLOCKS_MAX);
-  if (const char* be = getenv("WN_WGRAD_PATCH_BLOCKS")) blocks = atoi(be);
-  int split = std::max(1, (blocks + gx * gy / 2) / (gx * gy));
-  split = (int)std::min<long>(split, (long)N * H * nSeg);
+  const int split =
+      patch_split(work, BK * 16 * KS, gx * gy, WGRAD_PATCH16_BLOCKS_K,
+                  WGRAD_PATCH16_BLOCKS_MAX, (long)N * H * nSeg);
   hipLaunchKernelGGL((k_conv_wgrad_patch16<KS, BK, CH>),
-                     dim3(gx, gy, split), dim3(256), (size_t)G::LDS, stream,
-                     (const bf16_t*)dy.data_ptr(),
+                     dim3(gx, gy, split), dim3(256), (size_t)G::LDS_BYTES,
+                     stream, (const bf16_t*)dy.data_ptr(),
                      (const bf16_t*)x.data_ptr(), dw.data_ptr<float>(), N, H,
                      W, Kp, K, C, nSeg, zero16);
 }
 
+// cls: 64 (Cp and Kp multiples of 64), 32 (32 -> 32) or 16 (Cp = 16).
 void launch_wgrad_patch(const at::Tensor& dy, const at::Tensor& x,
                         at::Tensor& dw, int ks, int cls,
                         const bf16_t* zero16, hipStream_t stream) {
@@ -2143,76 +1307,25 @@ void launch_wgrad_patch(const at::Tensor& dy, const at::Tensor& x,
     ch = (pad112 < pad64) ? 112 : 64;
     if (force_ch == 64 || force_ch == 112) ch = force_ch;
   }
-  const bool bk32 = dy.size(3) == 32;  // cls 16: Kp = 32 or a multiple of 64
-  auto go = [&](auto ks_const) {
+  const int bk16 = dy.size(3) == 32 ? 32 : 64;  // cls 16: Kp = 32 or n*64
+  dispatch_int<3, 5, 7>(ks, "kernel size", [&](auto ks_const) {
     constexpr int KSV = decltype(ks_const)::value;
-    if (cls == 16 && bk32 && ch == 112)
-      launch_wgrad_patch16_t<KSV, 32, 112>(dy, x, dw, zero16, stream);
-    else if (cls == 16 && bk32)
-      launch_wgrad_patch16_t<KSV, 32, 64>(dy, x, dw, zero16, stream);
-    else if (cls == 16 && ch == 112)
-      launch_wgrad_patch16_t<KSV, 64, 112>(dy, x, dw, zero16, stream);
-    else if (cls == 16)
-      launch_wgrad_patch16_t<KSV, 64, 64>(dy, x, dw, zero16, stream);
-    else if (cls == 32)
-      launch_wgrad_patch_t<KSV, 32, 64>(dy, x, dw, zero16, stream);
-    else if (ch == 112)
-      launch_wgrad_patch_t<KSV, 64, 112>(dy, x, dw, zero16, stream);
-    else
-      launch_wgrad_patch_t<KSV, 64, 64>(dy, x, dw, zero16, stream);
-  };
-  switch (ks) {
-    case 3: go(std::integral_constant<int, 3>{}); break;
-    case 5: go(std::integral_constant<int, 5>{}); break;
-    case 7: go(std::integral_constant<int, 7>{}); break;
-    default: TORCH_CHECK(false, "unsupported kernel size ", ks);
-  }
+    dispatch_int<64, 112>(ch, "patch chunk length", [&](auto ch_const) {
+      constexpr int CHV = decltype(ch_const)::value;
+      if (cls == 16)
+        dispatch_int<32, 64>(bk16, "patch16 k tile", [&](auto bk_const) {
+          launch_wgrad_patch16_t<KSV, decltype(bk_const)::value, CHV>(
+              dy, x, dw, zero16, stream);
+        });
+      else if (cls == 32)
+        launch_wgrad_patch_t<KSV, 32, 64>(dy, x, dw, zero16, stream);
+      else
+        launch_wgrad_patch_t<KSV, 64, CHV>(dy, x, dw, zero16, stream);
+    });
+  });
 }
 
 }  // namespace
-
-// The dispatch decision conv2d_fwd would take for an (N,H,W,Cp) input and Kp
-// output channels: (kernel, BN, gz). Host only: launches nothing and touches
-// no device memory.
-std::tuple<std::string, int64_t, int64_t> conv2d_fwd_plan(
-    int64_t N, int64_t H, int64_t W, int64_t Cp, int64_t Kp, int64_t ks) {
-  TORCH_CHECK(ks == 1 || ks == 3 || ks == 5 || ks == 7,
-              "unsupported kernel size ", ks);
-  const ConvPlan p = conv_plan((long)(N * H * W), (int)Cp, (int)Kp, (int)ks);
-  const char* name = p.tier == TIER_SPLITK   ? "splitk"
-                     : p.tier == TIER_IGEMM8 ? "igemm8"
-                                             : "igemm";
-  return {name, p.BN, p.gz};
-}
-
-at::Tensor conv2d_fwd(const at::Tensor& x, const at::Tensor& wp,
-                      const c10::optional<at::Tensor>& bias, int64_t ks,
-                      int64_t Kp, int64_t Klog, int64_t act) {
-  TORCH_CHECK(x.is_cuda() && x.dtype() == at::kBFloat16 && x.dim() == 4,
-              "x must be CUDA bf16 NHWC");
-  TORCH_CHECK(wp.is_cuda() && wp.dtype() == at::kBFloat16);
-  TORCH_CHECK(x.is_contiguous() && wp.is_contiguous());
-  auto y = at::empty({x.size(0), x.size(1), x.size(2), Kp},
-                     x.options());
-  hipStream_t stream = at::cuda::getCurrentHIPStream();
-  switch (ks) {
-    case 1:
-      launch_conv_bn<1>(x, wp, bias, y, (int)Klog, (int)act, stream);
-      break;
-    case 3:
-      launch_conv_bn<3>(x, wp, bias, y, (int)Klog, (int)act, stream);
-      break;
-    case 5:
-      launch_conv_bn<5>(x, wp, bias, y, (int)Klog, (int)act, stream);
-      break;
-    case 7:
-      launch_conv_bn<7>(x, wp, bias, y, (int)Klog, (int)act, stream);
-      break;
-    default:
-      TORCH_CHECK(false, "unsupported kernel size ", ks);
-  }
-  return y;
-}
 
 void conv2d_wgrad(const at::Tensor& dy, const at::Tensor& x, at::Tensor& dw,
                   int64_t ks) {
@@ -2224,7 +1337,7 @@ void conv2d_wgrad(const at::Tensor& dy, const at::Tensor& x, at::Tensor& dw,
   const int Kp = dy.size(3);
   const int K = dw.size(0), C = dw.size(1);
   TORCH_CHECK(dw.size(2) == ks && dw.size(3) == ks);
-  hipStream_t stream0 = at::cuda::getCurrentHIPStream();
+  hipStream_t stream = at::cuda::getCurrentHIPStream();
   if (K <= 4) {  // output convs (K=3): VALU outer-product path
     const int RS = (int)(ks * ks);
     // m-slices per tap. A block pays a fixed LDS tree reduce + atomics, so
@@ -2243,48 +1356,36 @@ void conv2d_wgrad(const at::Tensor& dy, const at::Tensor& x, at::Tensor& dw,
     if (const char* ue = getenv("WN_WGRAD_SMALLK_U")) unroll = atoi(ue);
     const int MR = 256 / (Cp / 8);
     msplit = (int)std::min<long>(msplit, ((long)N * H * W + MR - 1) / MR);
-    auto go = [&](auto u_const) {
+    dispatch_int<1, 2, 4, 6>(unroll, "WN_WGRAD_SMALLK_U", [&](auto u_const) {
       constexpr int UV = decltype(u_const)::value;
       hipLaunchKernelGGL((k_wgrad_smallk<4, UV>), dim3(RS, msplit),
-                         dim3(256), 256 * 32 * sizeof(float), stream0,
+                         dim3(256), 256 * 32 * sizeof(float), stream,
                          (const bf16_t*)dy.data_ptr(),
                          (const bf16_t*)x.data_ptr(), dw.data_ptr<float>(),
                          N, H, W, Cp, log2i(Cp), Kp, K, C, (int)ks, msplit,
                          MagicDiv::make((unsigned)(H * W)).mul,
                          MagicDiv::make((unsigned)W).mul);
-    };
-    switch (unroll) {
-      case 1: go(std::integral_constant<int, 1>{}); break;
-      case 2: go(std::integral_constant<int, 2>{}); break;
-      case 4: go(std::integral_constant<int, 4>{}); break;
-      case 6: go(std::integral_constant<int, 6>{}); break;
-      default: TORCH_CHECK(false, "unsupported WN_WGRAD_SMALLK_U ", unroll);
-    }
+    });
     HIP_CHECK_LAST();
     return;
   }
-  // Patch kernel (one X row segment staged once for all KS dx taps) for the
-  // channel classes it is instantiated for. WN_WGRAD_PATCH=0 forces the old
-  // kernel everywhere, =1 the patch kernel wherever it is supported; unset,
-  // each (KS, Cp, Kp) class takes whichever measured faster.
-  static const int patch_mode = [] {
+  // Patch kernel (one X row segment staged once for all KS dx taps) for
+  // every channel class it is instantiated for: each measured faster than
+  // k_conv_wgrad on MI355X, the Cp = 16 tap-pair classes included (table:
+  // docs/KERNELS.md, wgrad section). WN_WGRAD_PATCH=0 forces k_conv_wgrad
+  // everywhere.
+  static const bool patch_off = [] {
     const char* e = getenv("WN_WGRAD_PATCH");
-    return e == nullptr ? -1 : (atoi(e) != 0 ? 1 : 0);
+    return e != nullptr && atoi(e) == 0;
   }();
-  if (patch_mode != 0 && ks >= 3) {
-    const int cls = (Cp % 64 == 0 && Kp % 64 == 0)           ? 64
-                    : (Cp == 32 && Kp == 32)                 ? 32
-                    : (Cp == 16 && (Kp == 32 || Kp % 64 == 0)) ? 16
+  const int cls = (Cp % 64 == 0 && Kp % 64 == 0)             ? 64
+                  : (Cp == 32 && Kp == 32)                   ? 32
+                  : (Cp == 16 && (Kp == 32 || Kp % 64 == 0)) ? 16
                                                              : 0;
-    if (cls != 0 && (patch_mode > 0 || wgrad_patch_wins((int)ks, Cp, Kp))) {
-      static thread_local at::Tensor zero16p;
-      if (!zero16p.defined() || zero16p.device() != x.device())
-        zero16p = at::zeros({8}, x.options());
-      launch_wgrad_patch(dy, x, dw, (int)ks, cls,
-                         (const bf16_t*)zero16p.data_ptr(), stream0);
-      HIP_CHECK_LAST();
-      return;
-    }
+  if (!patch_off && ks >= 3 && cls != 0) {
+    launch_wgrad_patch(dy, x, dw, (int)ks, cls, zero16_for(x), stream);
+    HIP_CHECK_LAST();
+    return;
   }
   const int KG = (int)(ks * ks) * Cp;
   const int BK = std::min(Kp, 128);
@@ -2294,55 +1395,31 @@ void conv2d_wgrad(const at::Tensor& dy, const at::Tensor& x, at::Tensor& dw,
   int split = std::max(1, 640 / std::max(1, gx * gy));
   const long nChunks = ((long)N * H * W + WG_CH - 1) / WG_CH;
   split = (int)std::min<long>(split, nChunks);
-  hipStream_t stream = at::cuda::getCurrentHIPStream();
-  const int cpk = (WG_CH / 4 * 72 + 16) / 8;  // image chunks per kblk
-  const int sa = ((BK / 16) * cpk + 255) / 256;
-  const int sb = (8 * cpk + 255) / 256;
-  const size_t lds = (size_t)2 * (sa + sb) * 256 * 8 * sizeof(bf16_t);
-  static thread_local at::Tensor zero16w;
-  if (!zero16w.defined() || zero16w.device() != x.device())
-    zero16w = at::zeros({8}, x.options());
+  const bf16_t* zptr = zero16_for(x);
   static const bool use_m32 = [] {
     const char* e = getenv("WN_WGRAD_M32");
     return e == nullptr || atoi(e) != 0;  // default ON; 0 = 16x16 path
   }();
-  auto launch = [&](auto ks_const, auto bk_const) {
-    constexpr int KSV = decltype(ks_const)::value;
-    constexpr int BKV = decltype(bk_const)::value;
-    constexpr int CHV = 64;
-    auto go = [&](auto m32_const) {
-      constexpr bool M32V = decltype(m32_const)::value;
-      hipLaunchKernelGGL((k_conv_wgrad<KSV, BKV, CHV, M32V>),
-                         dim3(gx, gy, split), dim3(256), lds, stream,
-                         (const bf16_t*)dy.data_ptr(),
-                         (const bf16_t*)x.data_ptr(), dw.data_ptr<float>(),
-                         N, H, W, Cp, log2i(Cp), Kp, K, C, split,
-                         MagicDiv::make((unsigned)(H * W)).mul,
-                         MagicDiv::make((unsigned)W).mul,
-                         (const bf16_t*)zero16w.data_ptr());
-    };
-    if (BKV >= 32 && use_m32)
-      go(std::integral_constant<bool, (BKV >= 32)>{});
-    else
-      go(std::false_type{});
-  };
-  auto launch_ks = [&](auto ks_const) {
-    if (BK == 128)
-      launch(ks_const, std::integral_constant<int, 128>{});
-    else if (BK == 64)
-      launch(ks_const, std::integral_constant<int, 64>{});
-    else if (BK == 32)
-      launch(ks_const, std::integral_constant<int, 32>{});
-    else
-      launch(ks_const, std::integral_constant<int, 16>{});
-  };
-  switch (ks) {
-    case 1: launch_ks(std::integral_constant<int, 1>{}); break;
-    case 3: launch_ks(std::integral_constant<int, 3>{}); break;
-    case 5: launch_ks(std::integral_constant<int, 5>{}); break;
-    case 7: launch_ks(std::integral_constant<int, 7>{}); break;
-    default: TORCH_CHECK(false, "unsupported kernel size ", ks);
-  }
+  dispatch_int<1, 3, 5, 7>((int)ks, "kernel size", [&](auto ks_const) {
+    // BK = min(Kp, 128) with Kp a power of two >= 16
+    dispatch_int_or<16, 128, 64, 32, 16>(BK, [&](auto bk_const) {
+      constexpr int KSV = decltype(ks_const)::value;
+      constexpr int BKV = decltype(bk_const)::value;
+      // the 32x32 MFMA path exists for BK >= 32
+      dispatch_int<0, 1>(BKV >= 32 && use_m32, "M32", [&](auto m32_const) {
+        constexpr bool M32V = BKV >= 32 && decltype(m32_const)::value != 0;
+        using G = WgradGeo<BKV, WG_CH>;
+        hipLaunchKernelGGL((k_conv_wgrad<KSV, BKV, WG_CH, M32V>),
+                           dim3(gx, gy, split), dim3(256),
+                           (size_t)G::LDS_BYTES, stream,
+                           (const bf16_t*)dy.data_ptr(),
+                           (const bf16_t*)x.data_ptr(), dw.data_ptr<float>(),
+                           N, H, W, Cp, log2i(Cp), Kp, K, C, split,
+                           MagicDiv::make((unsigned)(H * W)).mul,
+                           MagicDiv::make((unsigned)W).mul, zptr);
+      });
+    });
+  });
   HIP_CHECK_LAST();
 }
 
@@ -2370,38 +1447,4 @@ void bias_grad(const at::Tensor& dy, at::Tensor& db) {
                      part.data_ptr<float>(), db.data_ptr<float>(), Kp, K,
                      msplit);
   HIP_CHECK_LAST();
-}
-
-at::Tensor pack_weight_fwd(const at::Tensor& w, int64_t Kp, int64_t Cp) {
-  TORCH_CHECK(w.is_cuda() && w.dtype() == at::kFloat && w.dim() == 4);
-  TORCH_CHECK(w.is_contiguous());
-  const int K = w.size(0), C = w.size(1), R = w.size(2), S = w.size(3);
-  auto out = at::empty({Kp, (long)R * S * Cp},
-                       w.options().dtype(at::kBFloat16));
-  const long total = out.numel();
-  const int blocks = (int)std::min<long>(2048, (total + 255) / 256);
-  hipStream_t stream = at::cuda::getCurrentHIPStream();
-  hipLaunchKernelGGL(k_pack_fwd, dim3(blocks), dim3(256), 0, stream,
-                     w.data_ptr<float>(), (bf16_t*)out.data_ptr(), K, C, R, S,
-                     (int)Kp, (int)Cp);
-  HIP_CHECK_LAST();
-  return out;
-}
-
-at::Tensor pack_weight_dgrad(const at::Tensor& w, int64_t Kp, int64_t Cp) {
-  // output [Cp][RS*Kp]: dgrad conv consumes dY (channels Kp) and produces
-  // dX (channels Cp); weights rotated 180 and transposed.
-  TORCH_CHECK(w.is_cuda() && w.dtype() == at::kFloat && w.dim() == 4);
-  TORCH_CHECK(w.is_contiguous());
-  const int K = w.size(0), C = w.size(1), R = w.size(2), S = w.size(3);
-  auto out = at::empty({Cp, (long)R * S * Kp},
-                       w.options().dtype(at::kBFloat16));
-  const long total = out.numel();
-  const int blocks = (int)std::min<long>(2048, (total + 255) / 256);
-  hipStream_t stream = at::cuda::getCurrentHIPStream();
-  hipLaunchKernelGGL(k_pack_dgrad, dim3(blocks), dim3(256), 0, stream,
-                     w.data_ptr<float>(), (bf16_t*)out.data_ptr(), K, C, R, S,
-                     (int)Kp, (int)Cp);
-  HIP_CHECK_LAST();
-  return out;
 }

@@ -2,7 +2,8 @@
 every nn.Conv2d the reference runs (net.py:14-45,66-71 and the VGG19
 features) dispatches here on GPU.
 
-ConvBiasAct is the autograd wrapper around csrc/conv_mfma.hip: forward runs
+ConvBiasAct is the autograd wrapper around csrc/conv_fwd.hip and
+csrc/conv_wgrad.hip: forward runs
 the fused conv+bias+activation kernel on NHWC bf16; backward runs
 activation-backward, dgrad (the same implicit-GEMM kernel on rotated/
 transposed packed weights) and wgrad/bias-grad (atomic fp32 accumulation).
