@@ -10,6 +10,9 @@
 //     Also runs dgrad (conv of dY with rotated/transposed packed weights).
 //   - k_conv_igemm8<BN,KS>: 8-wave 256-row phase-split variant for big-M
 //     shapes (setprio-wrapped MFMA phases, counted vmcnt).
+//   - k_conv_patch<KS,BN,CC>: big-M k3/k5/k7 layers with 64/128 channels and
+//     H, W multiples of 16: a 16x16 output-pixel tile per block, the input
+//     patch staged into LDS once and the taps taken by shifted reads.
 //   - k_splitk_finalize<GZ>: sums the split-K slabs, bias + activation.
 // The weight-gradient kernels are in conv_wgrad.hip, weight packing in
 // conv_pack.hip; conv_common.h has the notes and host helpers they share.
@@ -192,9 +195,16 @@ WN_DEVFN void store_out(const ConvOut& o, long m, int k, float v, float bv,
 // whose first row / column are m0 + rW / kW (m0 stays apart so the row
 // offset is summed in 32 bits). D map of both MFMA shapes: col = lane % FR,
 // row = (r&3) + 8*(r>>2) + 4*(lane/FR) — for 16x16 that is lg*4 + r, li.
-template <bool SLAB, int FR, class Acc, int FM, int FN>
-WN_DEVFN void store_tile(const Acc (&acc)[FM][FN], long m0, int rW, int kW,
-                         int lane, const ConvOut& o) {
+// The row map turns a tile row into the GEMM row m it is stored at: GemmRows
+// for tiles of consecutive GEMM rows, PixelTileRows (k_conv_patch) for a
+// TW-wide tile of output pixels.
+struct GemmRows {
+  long m0;
+  WN_DEVFN long operator()(int r) const { return m0 + r; }
+};
+template <bool SLAB, int FR, class Acc, int FM, int FN, class RowMap>
+WN_DEVFN void store_tile(const Acc (&acc)[FM][FN], const RowMap& rows, int rW,
+                         int kW, int lane, const ConvOut& o) {
 #pragma unroll
   for (int fn = 0; fn < FN; ++fn) {
     const int k = kW + fn * FR + (lane & (FR - 1));
@@ -206,12 +216,17 @@ WN_DEVFN void store_tile(const Acc (&acc)[FM][FN], long m0, int rW, int kW,
 #pragma unroll
       for (int r = 0; r < FR * FR / 64; ++r) {
         const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane / FR);
-        long m = m0 + (rW + fm * FR + row);
+        long m = rows(rW + fm * FR + row);
         if (m >= o.M) continue;
         store_out<SLAB>(o, m, k, acc[fm][fn][r], bv, kpad);
       }
     }
   }
+}
+template <bool SLAB, int FR, class Acc, int FM, int FN>
+WN_DEVFN void store_tile(const Acc (&acc)[FM][FN], long m0, int rW, int kW,
+                         int lane, const ConvOut& o) {
+  store_tile<SLAB, FR>(acc, GemmRows{m0}, rW, kW, lane, o);
 }
 
 // ---------------------------------------------------------------------------
@@ -573,6 +588,266 @@ __global__ __launch_bounds__(512, 1) void k_conv_igemm8(
     store_tile<false, 16>(acc, m0, rW, kW, lane, out);
 }
 
+// ---------------------------------------------------------------------------
+// Patch-staged conv for big-M k3/k5/k7 layers with 64 / 128 channels.
+// k_conv_igemm8 streams a fresh 256x32 A tile through the LDS DMA for every
+// tap: an input pixel lands in LDS KS^2 times. Here a block owns a 16x16
+// tile of output pixels of one image and stages the (16+KS-1)^2 input patch
+// ONCE, all CC = Cp channels of it, as plain [pixel][CC] rows; the A fragment
+// of tap (dy, dx) is the tap-0 read with every lane moved by dy*PW + dx
+// pixel rows (A is K-contiguous, so plain ds_read_b128, no transpose read).
+//   - 512 threads = 8 waves as 4(M)x2(N): a wave owns 4 output rows of the
+//     tile (4 fragments of 16 pixels) x BN/2 channels, 16x16x32 MFMA.
+//   - K order: the igemm's own rsc = tap*Cp + c in 32-wide steps, so the
+//     sums are those of k_conv_igemm8 bit for bit. (Staging Cp = 128 as two
+//     64-channel chunks would halve the patch and keep two blocks per CU,
+//     but makes the order chunk-major: different fp32 rounding.)
+//   - B (packed weights) goes through a 3-deep fragment-major ring exactly
+//     as in k_conv_igemm8 (counted vmcnt, one tile in flight at a barrier);
+//     only the waves whose slots are inside the BN x 32 tile issue.
+//   - patch image: 128- or 256-byte pixel rows. A fragment read takes 16
+//     consecutive pixels x one 16 B chunk per 16-lane MFMA k-group;
+//     ds_read_b128 serves lanes in the groups {0-3,12-15,20-27},
+//     {4-11,16-19,28-31} (+32), i.e. two neighbouring chunks c, c^1 of
+//     interleaved pixel runs. The chunk index is XORed above its bit 0 with
+//     pixel bits (CC=64: pixel bits 1-2, CC=128: bits 0-2), which puts the 16
+//     lanes of a group on the 16 distinct 16 B columns of the 256 B bank row
+//     at every pixel shift (cp_frag_conflict_free). The XOR moves whole
+//     chunks, so the glds image stays lane-linear with the swizzle on the
+//     SOURCE chunk.
+// ---------------------------------------------------------------------------
+
+constexpr int cp_swz(int pix, int CC) {
+  return CC == 64 ? ((pix >> 1) & 3) << 1 : (pix & 7) << 1;
+}
+// byte offset of 16 B channel chunk ch of patch pixel pix
+constexpr int cp_off(int pix, int ch, int CC) {
+  return pix * CC * 2 + ((ch ^ cp_swz(pix, CC)) << 4);
+}
+// glds staging slot -> patch pixel / SOURCE channel chunk
+constexpr int cp_slot_pix(int slot, int CC) { return slot / (CC / 8); }
+constexpr int cp_slot_chunk(int slot, int CC) {
+  return (slot % (CC / 8)) ^ cp_swz(cp_slot_pix(slot, CC), CC);
+}
+// slot s lands at byte 16*s and the slots of a pixel cover its chunks once
+constexpr bool cp_image_linear(int NPIX, int CC) {
+  const int CPR = CC / 8;
+  for (int pix = 0; pix < NPIX; ++pix) {
+    unsigned seen = 0;
+    for (int c = 0; c < CPR; ++c) {
+      const int s = pix * CPR + c;
+      if (cp_slot_pix(s, CC) != pix) return false;
+      const int ch = cp_slot_chunk(s, CC);
+      if (ch < 0 || ch >= CPR) return false;
+      if (cp_off(pix, ch, CC) != 16 * s) return false;
+      seen |= 1u << ch;
+    }
+    if (seen != (1u << CPR) - 1) return false;
+  }
+  return true;
+}
+// the 16x16x32 A fragment read (lane = kgroup*16 + pixel, chunk = kb*4 +
+// kgroup) is conflict-free in each ds_read_b128 lane group at every shift
+constexpr bool cp_frag_conflict_free(int CC) {
+  for (int sh = 0; sh < 16; ++sh)
+    for (int kb = 0; kb < CC / 32; ++kb)
+      for (int g = 0; g < 4; ++g) {
+        unsigned used = 0;
+        for (int l = 0; l < 64; ++l) {
+          const int m = l & 31;
+          const bool first =
+              m < 4 || (m >= 12 && m < 16) || (m >= 20 && m < 28);
+          if ((l >> 5) * 2 + (first ? 0 : 1) != g) continue;
+          const int a = cp_off(sh + (l & 15), kb * 4 + (l >> 4), CC);
+          const unsigned bit = 1u << ((a / 16) % 16);
+          if (used & bit) return false;
+          used |= bit;
+        }
+        if (used != 0xffffu) return false;
+      }
+  return true;
+}
+
+template <int KS, int BN, int CC>
+struct ConvPatchGeo {
+  static constexpr int THREADS = 512;
+  static constexpr int TH = 16, TW = 16, BM = TH * TW;  // output pixel tile
+  static constexpr int PAD = KS / 2;
+  static constexpr int PH = TH + KS - 1, PW = TW + KS - 1, NPX = PH * PW;
+  static constexpr int PSLOTS = NPX * (CC / 8);
+  // wave-wide glds instructions (1 KiB each) that cover the patch; the
+  // surplus lanes of the last one land inside PBYTES
+  static constexpr int PINSTR = (PSLOTS + 63) / 64;
+  static constexpr int PBYTES = PINSTR * 1024;
+  static constexpr int SP = (PINSTR * 64 + THREADS - 1) / THREADS;
+  static constexpr int WMW = 4, WNW = 2;  // wave grid
+  static constexpr int FM = BM / WMW / 16, FN = BN / WNW / 16;
+  static constexpr int SLOTS_B = BN * 4;
+  static constexpr int LB = BN * 32;  // B tile elems (32 K)
+  static constexpr int RING = 3;
+  static constexpr int AHEAD = RING - 2;  // B tiles in flight at the wait
+  static constexpr int KB = CC / 32;      // K-steps per tap
+  static constexpr int LDS_BYTES = PBYTES + RING * LB * (int)sizeof(bf16_t);
+  static_assert(LDS_BYTES <= 160 * 1024);
+  // resident blocks per CU by the 160 KiB of LDS (2 for CC = 64, 1 for
+  // CC = 128); the launch bounds ask for 2 waves per SIMD per block
+  static constexpr int BLOCKS_PER_CU = LDS_BYTES <= 80 * 1024 ? 2 : 1;
+};
+
+// tile row r = py*TW + px of the block's output tile -> GEMM row
+struct PixelTileRows {
+  long m00;  // GEMM row of the tile's first pixel
+  int W;
+  WN_DEVFN long operator()(int r) const {
+    return m00 + (long)(r >> 4) * W + (r & 15);
+  }
+};
+
+template <int KS, int BN, int CC>
+__global__ __launch_bounds__(
+    512, (2 * ConvPatchGeo<KS, BN, CC>::BLOCKS_PER_CU)) void k_conv_patch(
+    const bf16_t* __restrict__ X,   // (N, H, W, Cp), Cp == CC
+    const bf16_t* __restrict__ Wp,  // [Kp][RS*Cp]
+    const float* __restrict__ Bias,
+    bf16_t* __restrict__ Y,         // (N, H, W, Kp); H % 16 == W % 16 == 0
+    int N, int H, int W, int Cp, int log2Cp, int Kp, int Klog, int act,
+    const bf16_t* __restrict__ Zero16) {
+  static_assert(WN_MFMA_KMAP == 0, "glds staging assumes KMAP 0");
+  using G = ConvPatchGeo<KS, BN, CC>;
+  constexpr int PAD = G::PAD, PW = G::PW, NPX = G::NPX, SP = G::SP;
+  constexpr int FM = G::FM, FN = G::FN, LB = G::LB, RING = G::RING;
+  constexpr int AHEAD = G::AHEAD, KB = G::KB;
+  constexpr int THREADS = G::THREADS;  // local: see k_conv_igemm8
+  static_assert(G::TW == 16 && (CC == 64 || CC == 128) && FM == 4,
+                "a fragment is one 16-pixel output row");
+  static_assert(cp_image_linear(NPX, CC),
+                "glds slot order != image chunk order");
+  static_assert(cp_frag_conflict_free(CC), "fragment read bank conflict");
+  // the last pixel a fragment read touches is the patch's last; the swizzle
+  // stays inside a pixel row
+  static_assert((G::TH - 1 + KS - 1) * PW + (G::TW - 1 + KS - 1) == NPX - 1 &&
+                NPX * CC * 2 <= G::PBYTES);
+  static_assert(G::SLOTS_B % 64 == 0 && G::SLOTS_B <= THREADS,
+                "whole waves stage the B tile, one slot per lane");
+  constexpr int KG = KS * KS * CC;
+  constexpr int nk = KG / 32;
+  const long M = (long)N * H * W;
+
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* lP = smem;                                           // patch
+  bf16_t* lB = reinterpret_cast<bf16_t*>(smem + G::PBYTES);  // RING x LB
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int wr = wid >> 1;
+  const int wc = wid & 1;
+  // block-uniform tile decode
+  const int tilesX = W / G::TW, tilesY = H / G::TH;
+  const int tx = blockIdx.x % tilesX;
+  const int ty = (blockIdx.x / tilesX) % tilesY;
+  const int n = blockIdx.x / (tilesX * tilesY);
+  const int oy0 = ty * G::TH, ox0 = tx * G::TW;
+  const int n0 = blockIdx.y * BN;
+
+  // The patch: every lane of every issued wave-wide glds sources either its
+  // pixel's (swizzled) 16 B chunk or Zero16 (halo outside the image, surplus
+  // slots); whole instructions past the patch are not issued.
+#pragma unroll
+  for (int s = 0; s < SP; ++s) {
+    const int sg = tid + s * THREADS;
+    if ((sg >> 6) < G::PINSTR) {  // wave-uniform
+      const int pix = cp_slot_pix(sg, CC);
+      const int py = pix / PW, px = pix - py * PW;
+      const int iy = oy0 + py - PAD, ix = ox0 + px - PAD;
+      const bf16_t* src = Zero16;
+      if (pix < NPX && iy >= 0 && iy < H && ix >= 0 && ix < W)
+        src = X + (((long)n * H + iy) * W + ix) * CC +
+              cp_slot_chunk(sg, CC) * 8;
+      glds16(src, reinterpret_cast<bf16_t*>(lP + sg * 16));
+    }
+  }
+
+  // B tile of K-step g, fragment-major
+  const FragSlot bf = frag_slot<false>(tid);
+  const bool bIssue = tid < G::SLOTS_B;  // wave-uniform
+  auto stage_b = [&](int buf, int g) {
+    if (bIssue)
+      glds16(conv_b_src(Wp, Zero16, true, n0 + bf.row, g * 32 + bf.koff, Kp,
+                        KG),
+             lB + buf * LB + tid * 8);
+  };
+
+  f32x4 acc[FM][FN];
+#pragma unroll
+  for (int a = 0; a < FM; ++a)
+#pragma unroll
+    for (int b = 0; b < FN; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int lg = lane >> 4, li = lane & 15;
+  // patch pixel of this lane's row of fragment 0 at tap (0, 0)
+  const int pix0 = wr * FM * PW + li;
+
+  for (int t = 0; t < RING - 1 && t < nk; ++t) stage_b(t, t);
+  wait_vmcnt<0>();
+  __builtin_amdgcn_s_barrier();
+
+  int g = 0, tapoff = 0, dx = 0;
+  for (int tap = 0; tap < KS * KS; ++tap) {
+    // kb = 0 addresses; kb flips chunk bits 2-3 (the swizzle touches the
+    // chunk above bit 0 and kgroup < 4), i.e. address bits 6-7
+    unsigned aAd[FM];
+#pragma unroll
+    for (int fm = 0; fm < FM; ++fm) {
+      const int pix = pix0 + fm * PW + tapoff;
+      aAd[fm] = (unsigned)(pix * CC * 2 + ((lg ^ cp_swz(pix, CC)) << 4));
+    }
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb, ++g) {
+      const int b = g % RING;
+      if (g + RING - 1 < nk) stage_b((b + RING - 1) % RING, g + RING - 1);
+      bf16x8 aF[FM], bF[FN];
+#pragma unroll
+      for (int fn = 0; fn < FN; ++fn)
+        bF[fn] = *reinterpret_cast<const bf16x8*>(
+            lB + b * LB + (((wc * FN + fn) * 4 + lg) * 16 + li) * 8);
+#pragma unroll
+      for (int ph = 0; ph < 2; ++ph) {
+#pragma unroll
+        for (int fm = ph * 2; fm < ph * 2 + 2; ++fm)
+          aF[fm] = *reinterpret_cast<const bf16x8*>(
+              lP + (aAd[fm] ^ (unsigned)(kb * 64)));
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int fm = ph * 2; fm < ph * 2 + 2; ++fm)
+#pragma unroll
+          for (int fn = 0; fn < FN; ++fn)
+            acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                aF[fm], bF[fn], acc[fm][fn], 0, 0, 0);
+        __builtin_amdgcn_s_setprio(0);
+      }
+      if (g + 1 < nk) {
+        wait_tiles<1, AHEAD>(min(nk - g - 2, AHEAD));
+        __builtin_amdgcn_s_barrier();
+      }
+    }
+    if (++dx == KS) {
+      dx = 0;
+      tapoff += PW - (KS - 1);
+    } else {
+      ++tapoff;
+    }
+  }
+
+  // epilogue: the shared bias/activation/pad path over a pixel-tile row map
+  const ConvOut out{Bias, Y, nullptr, M, Kp, Klog, act};
+  const PixelTileRows rows{((long)n * H + oy0) * W + ox0, W};
+  store_tile<false, 16>(acc, rows, wr * (G::BM / G::WMW),
+                        n0 + wc * (BN / G::WNW), lane, out);
+}
+
 // Split-K finalize: Y = act(sum over gz slabs of Y32 + bias), pad zeroed.
 // GZ is a template constant so all slab loads issue in parallel (the
 // runtime-bounded loop serialized up to 8 dependent ~500-cycle loads per
@@ -613,7 +888,12 @@ namespace {
 // Which forward kernel a conv shape runs on, and on what grid. The single
 // source of the dispatch rule: launch_conv_bn launches what this returns and
 // conv2d_fwd_plan reports it to the tests.
-enum ConvTier { TIER_IGEMM = 0, TIER_SPLITK = 1, TIER_IGEMM8 = 2 };
+enum ConvTier {
+  TIER_IGEMM = 0,
+  TIER_SPLITK = 1,
+  TIER_IGEMM8 = 2,
+  TIER_PATCH = 3
+};
 
 struct ConvPlan {
   ConvTier tier;
@@ -623,7 +903,34 @@ struct ConvPlan {
   int gz;      // split-K slices (1 unless tier == TIER_SPLITK)
 };
 
-inline ConvPlan conv_plan(long M, int Cp, int Kp, int ks) {
+// k_conv_patch is instantiated for KS 3/5/7 with Cp and Kp each 64 or 128.
+inline bool conv_patch_instantiated(int ks, int Cp, int Kp) {
+  return (ks == 3 || ks == 5 || ks == 7) && (Cp == 64 || Cp == 128) &&
+         (Kp == 64 || Kp == 128);
+}
+
+// Classes where k_conv_patch measured faster than k_conv_igemm8 in the
+// per-shape A/B (docs/KERNELS.md, k_conv_patch table): a class is listed only
+// if every patch repeat beat the fastest igemm8 repeat at 112^2 and 256^2.
+// Today that is every instantiated class (1.01-2.1x; the narrowest is
+// k3 128->128 at 112^2, 136.8 us against 138.4).
+inline bool conv_patch_wins(int ks, int Cp, int Kp) {
+  return conv_patch_instantiated(ks, Cp, Kp);
+}
+
+// WN_CONV_PATCH, read once per process: 0 disables the patch tier, 1 forces
+// it wherever it is instantiated and eligible, unset (-1) follows
+// conv_patch_wins.
+inline int conv_patch_knob() {
+  static const int knob = [] {
+    const char* e = getenv("WN_CONV_PATCH");
+    return e ? (atoi(e) != 0 ? 1 : 0) : -1;
+  }();
+  return knob;
+}
+
+inline ConvPlan conv_plan(int N, int H, int W, int Cp, int Kp, int ks) {
+  const long M = (long)N * H * W;
   ConvPlan p;
   p.BN = Kp >= 128 ? 128 : Kp == 64 ? 64 : Kp == 32 ? 32 : 16;
   p.gx = (int)((M + 127) / 128);
@@ -652,6 +959,14 @@ inline ConvPlan conv_plan(long M, int Cp, int Kp, int ks) {
       return e ? atol(e) : 16384L;
     }();
     if (M >= m8_thresh) p.tier = TIER_IGEMM8;
+  }
+  // The patch tier takes over from igemm8 only: whole 16x16 pixel tiles and
+  // an instantiated class, by the knob or the measured table.
+  if (p.tier == TIER_IGEMM8 && conv_patch_instantiated(ks, Cp, Kp) &&
+      H % 16 == 0 && W % 16 == 0) {
+    const int knob = conv_patch_knob();
+    if (knob == 1 || (knob == -1 && conv_patch_wins(ks, Cp, Kp)))
+      p.tier = TIER_PATCH;
   }
   return p;
 }
@@ -683,7 +998,7 @@ void launch_conv_bn(const at::Tensor& x, const at::Tensor& wp,
   const long M = (long)N * H * W;
   const float* bptr =
       bias.has_value() ? bias->data_ptr<float>() : nullptr;
-  const ConvPlan plan = conv_plan(M, Cp, Kp, KS);
+  const ConvPlan plan = conv_plan(N, H, W, Cp, Kp, KS);
   const int gy = plan.gy, gz = plan.gz;
   const bf16_t* zptr = zero16_for(x);
 
@@ -715,6 +1030,23 @@ void launch_conv_bn(const at::Tensor& x, const at::Tensor& wp,
       });
       return;
     }
+    if constexpr (BN >= 64 && KS >= 3) {
+      if (plan.tier == TIER_PATCH) {  // big-M, whole 16x16 tiles
+        dispatch_int<64, 128>(Cp, "k_conv_patch Cp", [&](auto cc_const) {
+          constexpr int CC = decltype(cc_const)::value;
+          using G = ConvPatchGeo<KS, BN, CC>;
+          const dim3 grid(N * (H / G::TH) * (W / G::TW), gy);
+          with_args([&](auto... a) {
+            hipLaunchKernelGGL((k_conv_patch<KS, BN, CC>), grid,
+                               dim3(G::THREADS), (size_t)G::LDS_BYTES, stream,
+                               a...);
+          });
+        });
+        return;
+      }
+    }
+    TORCH_CHECK(plan.tier != TIER_PATCH, "k_conv_patch<", KS, ", ", BN,
+                "> is not instantiated");
     if constexpr (BN >= 64) {
       if (plan.tier == TIER_IGEMM8) {  // big-M: 8-wave 256-row phase-split
         // M32 exists for VAR 0 only and wins over WN_IGEMM8_VAR
@@ -754,9 +1086,11 @@ std::tuple<std::string, int64_t, int64_t> conv2d_fwd_plan(
     int64_t N, int64_t H, int64_t W, int64_t Cp, int64_t Kp, int64_t ks) {
   TORCH_CHECK(ks == 1 || ks == 3 || ks == 5 || ks == 7,
               "unsupported kernel size ", ks);
-  const ConvPlan p = conv_plan((long)(N * H * W), (int)Cp, (int)Kp, (int)ks);
+  const ConvPlan p =
+      conv_plan((int)N, (int)H, (int)W, (int)Cp, (int)Kp, (int)ks);
   const char* name = p.tier == TIER_SPLITK   ? "splitk"
                      : p.tier == TIER_IGEMM8 ? "igemm8"
+                     : p.tier == TIER_PATCH  ? "patch"
                                              : "igemm";
   return {name, p.BN, p.gz};
 }
