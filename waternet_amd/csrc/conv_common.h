@@ -1,5 +1,6 @@
-// Shared by conv_fwd.hip and conv_wgrad.hip: the fragment K-mapping switch
-// and the host-side helpers every tier's launch goes through.
+// Shared by conv_fwd.hip and conv_wgrad.hip: the fragment K-mapping switch,
+// the host-side helpers every tier's launch goes through, the counted waits
+// and the glds patch-image slot map of the patch kernels of both units.
 //
 // Design notes (MI355X), common to all conv kernels:
 //   - Cp (physical channels) is a power of two >= 16; pad channels are
@@ -58,3 +59,58 @@ inline const bf16_t* zero16_for(const at::Tensor& like) {
     zero16 = at::zeros({8}, like.options());
   return (const bf16_t*)zero16.data_ptr();
 }
+
+// Counted waits: the count is an "n" operand, so one template serves every
+// ring depth instead of a ladder of literal asm strings.
+template <int N>
+WN_DEVFN void wait_vmcnt() {
+  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit field");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+template <int N>
+WN_DEVFN void wait_lgkmcnt() {
+  static_assert(N >= 0 && N <= 15, "lgkmcnt is a 4-bit field");
+  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// ---------------------------------------------------------------------------
+// Patch image: plain [pixel][COLS] bf16 rows of COLS/8 16 B channel chunks,
+// filled by global_load_lds. glds writes lane-linearly (slot s lands at byte
+// 16*s), so a bank swizzle cannot move the destination; it XORs the chunk
+// INDEX inside a pixel row instead, which moves whole 16 B chunks, and each
+// slot sources the chunk that belongs where it lands. Swz::chunk_xor(pix,
+// COLS) is the XOR of a pixel row; it is a policy of the READ instruction the
+// image serves, and each kernel proves its own reads conflict-free on off().
+// ---------------------------------------------------------------------------
+template <class Swz>
+struct PatchImage {
+  // byte offset of 16 B channel chunk `chunk` of pixel row `pix`
+  static constexpr int off(int pix, int chunk, int COLS) {
+    return pix * COLS * 2 + ((chunk ^ Swz::chunk_xor(pix, COLS)) << 4);
+  }
+  // glds staging slot -> image pixel row / SOURCE 16 B channel chunk
+  static constexpr int slot_pix(int slot, int COLS) {
+    return slot / (COLS / 8);
+  }
+  static constexpr int slot_chunk(int slot, int COLS) {
+    return (slot % (COLS / 8)) ^ Swz::chunk_xor(slot_pix(slot, COLS), COLS);
+  }
+  // the slot map lands slot s at byte 16*s and covers every chunk of every
+  // pixel row exactly once (lane-linear glds image)
+  static constexpr bool linear(int NPIX, int COLS) {
+    const int CPR = COLS / 8;
+    for (int pix = 0; pix < NPIX; ++pix) {
+      unsigned seen = 0;
+      for (int c = 0; c < CPR; ++c) {
+        const int s = pix * CPR + c;
+        if (slot_pix(s, COLS) != pix) return false;
+        const int ch = slot_chunk(s, COLS);
+        if (ch < 0 || ch >= CPR) return false;
+        if (off(pix, ch, COLS) != 16 * s) return false;
+        seen |= 1u << ch;
+      }
+      if (seen != (1u << CPR) - 1) return false;
+    }
+    return true;
+  }
+};

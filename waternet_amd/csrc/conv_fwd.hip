@@ -142,11 +142,6 @@ WN_DEVFN void glds16(const bf16_t* src, bf16_t* dst) {
   __builtin_amdgcn_global_load_lds(src, dst, 16, 0, 0);
 }
 
-template <int N>
-WN_DEVFN void wait_vmcnt() {
-  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit field");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 // Wait until at most `tiles` (<= MAXT) staged tiles of GPS glds per thread
 // each remain outstanding.
 template <int GPS, int MAXT>
@@ -617,35 +612,13 @@ __global__ __launch_bounds__(512, 1) void k_conv_igemm8(
 //     SOURCE chunk.
 // ---------------------------------------------------------------------------
 
-constexpr int cp_swz(int pix, int CC) {
-  return CC == 64 ? ((pix >> 1) & 3) << 1 : (pix & 7) << 1;
-}
-// byte offset of 16 B channel chunk ch of patch pixel pix
-constexpr int cp_off(int pix, int ch, int CC) {
-  return pix * CC * 2 + ((ch ^ cp_swz(pix, CC)) << 4);
-}
-// glds staging slot -> patch pixel / SOURCE channel chunk
-constexpr int cp_slot_pix(int slot, int CC) { return slot / (CC / 8); }
-constexpr int cp_slot_chunk(int slot, int CC) {
-  return (slot % (CC / 8)) ^ cp_swz(cp_slot_pix(slot, CC), CC);
-}
-// slot s lands at byte 16*s and the slots of a pixel cover its chunks once
-constexpr bool cp_image_linear(int NPIX, int CC) {
-  const int CPR = CC / 8;
-  for (int pix = 0; pix < NPIX; ++pix) {
-    unsigned seen = 0;
-    for (int c = 0; c < CPR; ++c) {
-      const int s = pix * CPR + c;
-      if (cp_slot_pix(s, CC) != pix) return false;
-      const int ch = cp_slot_chunk(s, CC);
-      if (ch < 0 || ch >= CPR) return false;
-      if (cp_off(pix, ch, CC) != 16 * s) return false;
-      seen |= 1u << ch;
-    }
-    if (seen != (1u << CPR) - 1) return false;
+// chunk-index XOR of a patch pixel row (slot map: PatchImage, conv_common.h)
+struct CpSwz {
+  static constexpr int chunk_xor(int pix, int CC) {
+    return CC == 64 ? ((pix >> 1) & 3) << 1 : (pix & 7) << 1;
   }
-  return true;
-}
+};
+using CpImage = PatchImage<CpSwz>;
 // the 16x16x32 A fragment read (lane = kgroup*16 + pixel, chunk = kb*4 +
 // kgroup) is conflict-free in each ds_read_b128 lane group at every shift
 constexpr bool cp_frag_conflict_free(int CC) {
@@ -658,7 +631,7 @@ constexpr bool cp_frag_conflict_free(int CC) {
           const bool first =
               m < 4 || (m >= 12 && m < 16) || (m >= 20 && m < 28);
           if ((l >> 5) * 2 + (first ? 0 : 1) != g) continue;
-          const int a = cp_off(sh + (l & 15), kb * 4 + (l >> 4), CC);
+          const int a = CpImage::off(sh + (l & 15), kb * 4 + (l >> 4), CC);
           const unsigned bit = 1u << ((a / 16) % 16);
           if (used & bit) return false;
           used |= bit;
@@ -720,7 +693,7 @@ __global__ __launch_bounds__(
   constexpr int THREADS = G::THREADS;  // local: see k_conv_igemm8
   static_assert(G::TW == 16 && (CC == 64 || CC == 128) && FM == 4,
                 "a fragment is one 16-pixel output row");
-  static_assert(cp_image_linear(NPX, CC),
+  static_assert(CpImage::linear(NPX, CC),
                 "glds slot order != image chunk order");
   static_assert(cp_frag_conflict_free(CC), "fragment read bank conflict");
   // the last pixel a fragment read touches is the patch's last; the swizzle
@@ -757,13 +730,13 @@ __global__ __launch_bounds__(
   for (int s = 0; s < SP; ++s) {
     const int sg = tid + s * THREADS;
     if ((sg >> 6) < G::PINSTR) {  // wave-uniform
-      const int pix = cp_slot_pix(sg, CC);
+      const int pix = CpImage::slot_pix(sg, CC);
       const int py = pix / PW, px = pix - py * PW;
       const int iy = oy0 + py - PAD, ix = ox0 + px - PAD;
       const bf16_t* src = Zero16;
       if (pix < NPX && iy >= 0 && iy < H && ix >= 0 && ix < W)
         src = X + (((long)n * H + iy) * W + ix) * CC +
-              cp_slot_chunk(sg, CC) * 8;
+              CpImage::slot_chunk(sg, CC) * 8;
       glds16(src, reinterpret_cast<bf16_t*>(lP + sg * 16));
     }
   }
@@ -800,7 +773,7 @@ __global__ __launch_bounds__(
 #pragma unroll
     for (int fm = 0; fm < FM; ++fm) {
       const int pix = pix0 + fm * PW + tapoff;
-      aAd[fm] = (unsigned)(pix * CC * 2 + ((lg ^ cp_swz(pix, CC)) << 4));
+      aAd[fm] = (unsigned)CpImage::off(pix, lg, CC);
     }
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb, ++g) {

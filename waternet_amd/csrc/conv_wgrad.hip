@@ -10,12 +10,15 @@
 //     KS dx taps taken by row-shifted tr reads, LDS-transposed epilogue so
 //     the atomics are contiguous.
 //   - k_conv_wgrad_patch16<KS,BK,CH>: the same for Cp = 16, two taps per
-//     MFMA.
+//     MFMA. Both patch kernels are wgrad_patch_body (ownership, staging, A
+//     base, k-step ring, slab epilogue) with their own B-fragment policy, and
+//     share launch_wgrad_patch_t.
 //   - k_wgrad_smallk: VALU outer-product path for K <= 4 output convs.
 //   - k_bias_grad(+_reduce): slab-partial column sums of dY.
 //   - k_probe_tr(+_raw): ds_read_b64_tr_b16 semantics probes for the tests.
 // Every kernel with dynamic LDS takes its tile constants from a Geo struct,
-// and its launch takes LDS_BYTES from the same struct.
+// and its launch takes LDS_BYTES from the same struct. The counted waits and
+// the glds patch-image slot map (PatchImage) are in conv_common.h.
 
 #include "conv_common.h"
 
@@ -93,6 +96,19 @@ WN_DEVFN bf16x4 ds_tr16(unsigned addr) {
   // hipcc hoists the first tr read above the LDS fill — measured garbage).
   asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr) : "memory");
   return v;
+}
+
+// dW[k][c][dy][dx] += v for GEMM element (k, rsc = tap*Cp + c); rows past K,
+// columns past KG and pad channels are dropped.
+template <int KS>
+WN_DEVFN void wgrad_scatter_add(float* dW, int k, int rsc, float v, int K,
+                                int KG, int C, int Cp, int log2Cp) {
+  if (k >= K || rsc >= KG) return;
+  const int tap = rsc >> log2Cp;
+  const int c = rsc & (Cp - 1);
+  if (c >= C) return;
+  const int dy = tap / KS, dx = tap - (tap / KS) * KS;
+  atomicAdd(&dW[(((long)k * C + c) * KS + dy) * KS + dx], v);
 }
 
 // k_conv_wgrad tile geometry: BK x 128 output tile, m-chunks of CH.
@@ -291,16 +307,10 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad(
         if (kst + 1 < KST) rdk(kst + 1, ring ^ 1);
         // wait for THIS kstep's reads only; the next kstep's RPK stay
         // in flight under the MFMAs
-        if (kst + 1 < KST) {
-          if constexpr (RPK == 8)
-            asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
-          else if constexpr (RPK == 6)
-            asm volatile("s_waitcnt lgkmcnt(6)" ::: "memory");
-          else
-            asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-        } else {
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        }
+        if (kst + 1 < KST)
+          wait_lgkmcnt<RPK>();
+        else
+          wait_lgkmcnt<0>();
         __builtin_amdgcn_sched_barrier(0);
 
 #pragma unroll
@@ -337,7 +347,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad(
           bT[s2][f][1] = ds_tr16(base + TR_MBS * 2);
         }
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      wait_lgkmcnt<0>();
       __builtin_amdgcn_sched_barrier(0);  // keep MFMAs below the wait
 #pragma unroll
       for (int s2 = 0; s2 < CH / 32; ++s2)
@@ -366,18 +376,11 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad(
       for (int r = 0; r < 16; ++r) {
         const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
         const int k = kt0 + wr * (BK / WR) + fa * 32 + row;
-        if (k >= K) continue;
 #pragma unroll
-        for (int fb = 0; fb < FR32; ++fb) {
-          const int rsc = rt0 + wc * (BR / WC) + fb * 32 + (lane & 31);
-          if (rsc >= KG) continue;
-          const int tap = rsc >> log2Cp;
-          const int c = rsc & (Cp - 1);
-          if (c >= C) continue;
-          const int dy_ = tap / KS, dx_ = tap - (tap / KS) * KS;
-          atomicAdd(&dW[(((long)k * C + c) * KS + dy_) * KS + dx_],
-                    acc32[fa][fb][r]);
-        }
+        for (int fb = 0; fb < FR32; ++fb)
+          wgrad_scatter_add<KS>(
+              dW, k, rt0 + wc * (BR / WC) + fb * 32 + (lane & 31),
+              acc32[fa][fb][r], K, KG, C, Cp, log2Cp);
       }
     }
     return;
@@ -388,19 +391,11 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad(
   for (int fa = 0; fa < FK; ++fa) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      int k = kt0 + (wr * FK + fa) * 16 + lg * 4 + r;
-      if (k >= K) continue;
+      const int k = kt0 + (wr * FK + fa) * 16 + lg * 4 + r;
 #pragma unroll
-      for (int fb = 0; fb < FR; ++fb) {
-        int rsc = rt0 + (wc * FR + fb) * 16 + li;
-        if (rsc >= KG) continue;
-        int tap = rsc >> log2Cp;
-        int c = rsc & (Cp - 1);
-        if (c >= C) continue;
-        int dy = tap / KS, dx = tap - (tap / KS) * KS;
-        float v = acc[fa][fb][r];
-        atomicAdd(&dW[(((long)k * C + c) * KS + dy) * KS + dx], v);
-      }
+      for (int fb = 0; fb < FR; ++fb)
+        wgrad_scatter_add<KS>(dW, k, rt0 + (wc * FR + fb) * 16 + li,
+                              acc[fa][fb][r], K, KG, C, Cp, log2Cp);
     }
   }
 }
@@ -435,37 +430,30 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad(
 //     (BK=CT=64: 2x2x1; BK=CT=32: 1x1x4, each wave every 4th k-step).
 //   - per k-step: 2 A tr reads shared by all KS taps + 2*KS B tr reads,
 //     KS v_mfma_f32_32x32x16_bf16, 2-deep ring with counted lgkmcnt.
+//
+// k_conv_wgrad_patch16 (below) is the same scheme for 16-channel images.
+// Ownership, staging, the A tr base, the k-step ring and the slab epilogue
+// are written once (PatchOwner, PatchStager, patch_a_base, patch_chunk_mma,
+// patch_slab_drain, driven by wgrad_patch_body); a kernel supplies its Geo
+// struct, its B-fragment policy (PatchTapFrags / PatchPairFrags) and the
+// static_asserts about its own images.
 // ---------------------------------------------------------------------------
 
-// byte offset of (pixel row, column) inside a [pixel][COLS] bf16 image
-constexpr int pt_swz(int pix, int COLS) {
-  return COLS == 64 ? ((pix >> 1) & 1) << 6 : 0;
-}
-constexpr int pt_off(int pix, int col, int COLS) {
-  return pix * COLS * 2 + ((col * 2) ^ pt_swz(pix, COLS));
-}
-// glds staging slot -> image pixel row / SOURCE 16 B channel chunk
-constexpr int pt_slot_pix(int slot, int COLS) { return slot / (COLS / 8); }
-constexpr int pt_slot_chunk(int slot, int COLS) {
-  return (slot % (COLS / 8)) ^ (pt_swz(pt_slot_pix(slot, COLS), COLS) >> 4);
-}
-// the slot map lands slot s at byte 16*s and covers every chunk of every
-// pixel row exactly once (lane-linear glds image)
-constexpr bool pt_image_linear(int NPIX, int COLS) {
-  const int CPR = COLS / 8;
-  for (int pix = 0; pix < NPIX; ++pix) {
-    unsigned seen = 0;
-    for (int c = 0; c < CPR; ++c) {
-      const int s = pix * CPR + c;
-      if (pt_slot_pix(s, COLS) != pix) return false;
-      const int ch = pt_slot_chunk(s, COLS);
-      if (ch < 0 || ch >= CPR) return false;
-      if (pt_off(pix, ch * 8, COLS) != 16 * s) return false;
-      seen |= 1u << ch;
-    }
-    if (seen != (1u << CPR) - 1) return false;
+// chunk-index XOR of a pixel row of the wgrad images (slot map: PatchImage,
+// conv_common.h): byte bit 6 = chunk bit 2 with pixel bit 1 at 128 B rows
+struct PtSwz {
+  static constexpr int chunk_xor(int pix, int COLS) {
+    return COLS == 64 ? ((pix >> 1) & 1) << 2 : 0;
   }
-  return true;
+};
+using PtImage = PatchImage<PtSwz>;
+// the XOR as a byte offset inside a row, for the per-lane read bases
+constexpr int pt_swz(int pix, int COLS) {
+  return PtSwz::chunk_xor(pix, COLS) << 4;
+}
+// byte offset of (pixel row, column) inside a [pixel][COLS] bf16 image
+constexpr int pt_off(int pix, int col, int COLS) {
+  return PtImage::off(pix, col >> 3, COLS) + (col & 7) * 2;
 }
 // the 32x32x16 transposed read (per 32-lane half: 2 column blocks x 4
 // pixel rows x 4 8-byte pieces) is bank-conflict-free at every pixel shift
@@ -486,16 +474,24 @@ constexpr bool pt_tr_conflict_free(int COLS, int maxShift) {
   return true;
 }
 
-template <int KS, int BK, int CT, int CH>
-struct PatchGeo {
-  static constexpr int WR = BK / 32, WC = CT / 32;  // wave grid over the tile
+// Tile constants of a patch kernel: BK x CT tile, chunks of CH pixels, NPX
+// staged patch pixels per chunk. 4 waves = WR x WC 32x32 quadrants x WK
+// k-step interleave. The waves walk PXA >= CH pixel rows (whole k-steps for
+// each of the WK; PXA == CH where WK divides CH/16) and the images are staged
+// that long, the rows past the chunk sourced from the zero buffer, so a
+// padded k-step adds 0.
+template <int KS_, int BK_, int CT_, int CH_, int NPX_>
+struct PatchGeoBase {
+  static constexpr int KS = KS_, BK = BK_, CT = CT_, CH = CH_, NPX = NPX_;
+  static constexpr int WR = BK / 32, WC = CT >= 32 ? CT / 32 : 1;
   static constexpr int WK = 4 / (WR * WC);  // waves interleaving k-steps
   static constexpr int KST = CH / 16;       // k-steps per chunk
-  static constexpr int KSTW = KST / WK;     // k-steps per wave
-  static constexpr int NPX = CH + KS - 1;   // patch pixels (2*PAD halo)
+  static constexpr int KSTW = (KST + WK - 1) / WK;  // k-steps per wave
+  static constexpr int PXA = KSTW * WK * 16;  // pixel rows the waves walk
   static constexpr int ACPR = BK / 8, BCPR = CT / 8;  // 16 B chunks per row
   static constexpr int ASLOTS = CH * ACPR, BSLOTS = NPX * BCPR;
-  static constexpr int SA = (ASLOTS + 255) / 256, SB = (BSLOTS + 255) / 256;
+  static constexpr int SA = (PXA * ACPR + 255) / 256;
+  static constexpr int SB = ((PXA - CH + NPX) * BCPR + 255) / 256;
   static constexpr int ABYTES = SA * 256 * 16;  // padded: surplus slots stay
   static constexpr int BBYTES = SB * 256 * 16;  // inside
   static constexpr int SLABN = WR * 8 * CT * KS;  // floats per slab copy
@@ -505,37 +501,227 @@ struct PatchGeo {
                                              : WK * SLABN * 4;
 };
 
+// 32/64-channel tiles: the patch is the chunk plus the 2*PAD halo
 template <int KS, int BK, int CT, int CH>
-__global__ __launch_bounds__(256, 2) void k_conv_wgrad_patch(
-    const bf16_t* __restrict__ dY,  // (N,H,W,Kp)
-    const bf16_t* __restrict__ X,   // (N,H,W,Cp)
-    float* __restrict__ dW,         // (K, C, KS, KS) fp32, accumulated into
-    int N, int H, int W, int Cp, int Kp, int K, int C, int nSeg,
-    const bf16_t* __restrict__ Zero16w) {
+struct PatchGeo : PatchGeoBase<KS, BK, CT, CH, CH + KS - 1> {};
+
+// What a block owns: one dy tap row and the chunks [c0, c1) of the N * Hv *
+// nSeg whose input row oy + dy - PAD lies inside the image, as the
+// gridDim.z-way slice blockIdx.z. (n, oyv, seg) is the current chunk.
+struct PatchOwner {
+  int oyLo, Hv, c0, c1, n, oyv, seg;
+  // false: nothing owned (block-uniform; nothing staged or read yet)
+  WN_DEVFN bool init(int N, int H, int PAD, int dy_, int nSeg) {
+    oyLo = max(0, PAD - dy_);
+    Hv = min(H, H + PAD - dy_) - oyLo;
+    if (Hv <= 0) return false;
+    const int total = N * Hv * nSeg;
+    const int per = (total + (int)gridDim.z - 1) / (int)gridDim.z;
+    c0 = blockIdx.z * per;
+    c1 = min(total, c0 + per);
+    if (c0 >= c1) return false;
+    n = c0 / (Hv * nSeg);
+    oyv = (c0 - n * Hv * nSeg) / nSeg;
+    seg = c0 - (n * Hv + oyv) * nSeg;
+    return true;
+  }
+  WN_DEVFN void advance(int nSeg) {
+    if (++seg == nSeg) {
+      seg = 0;
+      if (++oyv == Hv) { oyv = 0; ++n; }
+    }
+  }
+  WN_DEVFN int oy() const { return oyLo + oyv; }
+};
+
+// glds staging of one chunk: dY [CH][BK] and the X patch [NPX][CT] of input
+// row oy + dy - PAD. Slot -> (pixel row, source chunk) is fixed per thread;
+// slots past the image, past the row end or outside the picture source the
+// 16 B zero buffer.
+template <class G>
+struct PatchStager {
+  static constexpr int PAD = G::KS / 2;
+  const bf16_t *dY, *X, *zero;
+  char *lA, *lB;  // 2 x ABYTES, 2 x BBYTES
+  int H, W, Kp, Cp, kt0, ct0, dy_, tid;
+  int aPix[G::SA], aCh[G::SA], bPix[G::SB], bCh[G::SB];
+
+  WN_DEVFN void init_slots() {
+#pragma unroll
+    for (int s = 0; s < G::SA; ++s) {
+      const int sg = tid + s * 256;
+      aPix[s] = (sg < G::ASLOTS) ? PtImage::slot_pix(sg, G::BK)
+                                 : (1 << 28);  // -> zero
+      aCh[s] = PtImage::slot_chunk(sg, G::BK) * 8;
+    }
+#pragma unroll
+    for (int s = 0; s < G::SB; ++s) {
+      const int sg = tid + s * 256;
+      bPix[s] = (sg < G::BSLOTS) ? PtImage::slot_pix(sg, G::CT) - PAD
+                                 : (1 << 28);
+      bCh[s] = PtImage::slot_chunk(sg, G::CT) * 8;
+    }
+  }
+  WN_DEVFN void operator()(int buf, int n_, int oy, int sg_) const {
+    const int ox0 = sg_ * G::CH;
+    const long rowm = ((long)n_ * H + oy) * W;
+    const long rowx = ((long)n_ * H + oy + dy_ - PAD) * W;
+#pragma unroll
+    for (int s = 0; s < G::SA; ++s) {
+      const bf16_t* src = zero;
+      const int ox = ox0 + aPix[s];
+      if (ox < W) src = dY + (rowm + ox) * Kp + kt0 + aCh[s];
+      __builtin_amdgcn_global_load_lds(
+          src, lA + buf * G::ABYTES + (tid + s * 256) * 16, 16, 0, 0);
+    }
+#pragma unroll
+    for (int s = 0; s < G::SB; ++s) {
+      const bf16_t* src = zero;
+      const int ix = ox0 + bPix[s];
+      if (ix >= 0 && ix < W) src = X + (rowx + ix) * Cp + ct0 + bCh[s];
+      __builtin_amdgcn_global_load_lds(
+          src, lB + buf * G::BBYTES + (tid + s * 256) * 16, 16, 0, 0);
+    }
+  }
+};
+
+// Per-lane tr-read geometry. Lane l reads column (l&31) of its 32-wide
+// block: 16-column half hb = (l>>4)&1, reduction pixels (l>>5)*8 + 4h + e;
+// inside the 16-lane group, lane 4q+p addresses row q, columns 4p..4p+3.
+// rowl is the lane's pixel row in its wave's first k-step.
+struct PatchLane {
+  int q, hb, rowl;
+  WN_DEVFN PatchLane(int lane, int wk)
+      : q((lane & 15) >> 2), hb((lane >> 4) & 1),
+        rowl(wk * 16 + (lane >> 5) * 8 + q) {}
+};
+// A (dY) base: the pixel of a read is rowl + 16*kst + 4h, so q alone feeds
+// the swizzle
+template <int BK>
+WN_DEVFN unsigned patch_a_base(const char* lA, PatchLane L, int lane, int wr) {
+  const int acol2 = (wr * 32 + L.hb * 16 + (lane & 3) * 4) * 2;
+  return (unsigned)(unsigned long long)lA +
+         (unsigned)(L.rowl * BK * 2 + (acol2 ^ pt_swz(L.q, BK)));
+}
+
+// B fragments of a 32/64-channel patch: fragment t is tap dx = t, the dx = 0
+// read moved t pixel rows. The pixel of a read is rowl + (16*kst + 4h + dx):
+// only (q + dx) & 2 feeds the swizzle, so 4 bases (dx & 3) cover every shift.
+template <int KS, int CT>
+struct PatchTapFrags {
+  static constexpr int NB = KS;
+  unsigned b[4];
+  int col;  // D column of the lane inside the CT tile
+  WN_DEVFN PatchTapFrags(const char* lB, PatchLane L, int lane, int wc)
+      : col(wc * 32 + (lane & 31)) {
+    const int bcol2 = (wc * 32 + L.hb * 16 + (lane & 3) * 4) * 2;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      b[c] = (unsigned)(unsigned long long)lB +
+             (unsigned)(L.rowl * CT * 2 + (bcol2 ^ pt_swz(L.q + c, CT)));
+  }
+  WN_DEVFN PatchTapFrags at(unsigned bufOff) const {
+    PatchTapFrags f = *this;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) f.b[i] += bufOff;
+    return f;
+  }
+  // LDS address of fragment t for the 4-pixel read at pixel p
+  WN_DEVFN unsigned addr(int t, int p) const {
+    return b[t & 3] + (unsigned)((p + t) * CT * 2);
+  }
+  // element r of every accumulator -> slab row [c][dx] of one k
+  WN_DEVFN void scatter(float* row, const f32x16 (&acc)[NB], int r) const {
+    float* dst = row + col * KS;
+#pragma unroll
+    for (int dx = 0; dx < KS; ++dx) dst[dx] = acc[dx][r];
+  }
+};
+
+// One chunk's MFMAs: KSTW k-steps through a 2-deep ring of tr reads. Issue
+// order inside a k-step is part of the algorithm: the two A reads, then the
+// B fragments in ascending t, each as a (row, row+4) pair. LDS reads return
+// in issue order, so waiting until RPK are outstanding retires exactly this
+// k-step's reads and leaves the next one's in flight under the MFMAs.
+template <class G, class BF>
+WN_DEVFN void patch_chunk_mma(f32x16 (&acc)[BF::NB], unsigned aB,
+                              const BF& bf) {
+  constexpr int NB = BF::NB, BK = G::BK, WK = G::WK, KSTW = G::KSTW;
+  constexpr int RPK = 2 + 2 * NB;  // tr reads per k-step
+  bf16x4 aT[2][2], bT[2][NB][2];   // 2-deep k-step ring
+  auto rdk = [&](int i, int ring) {
+    const int p0 = i * WK * 16;  // first pixel of this wave's i-th k-step
+    aT[ring][0] = ds_tr16(aB + (unsigned)(p0 * BK * 2));
+    aT[ring][1] = ds_tr16(aB + (unsigned)((p0 + 4) * BK * 2));
+#pragma unroll
+    for (int t = 0; t < NB; ++t) {
+      bT[ring][t][0] = ds_tr16(bf.addr(t, p0));
+      bT[ring][t][1] = ds_tr16(bf.addr(t, p0 + 4));
+    }
+  };
+  rdk(0, 0);
+#pragma unroll
+  for (int i = 0; i < KSTW; ++i) {
+    const int ring = i & 1;
+    if (i + 1 < KSTW) {
+      rdk(i + 1, ring ^ 1);
+      // lgkmcnt saturates at 15: KS = 7's 16 reads in flight wait for one
+      // more than needed
+      wait_lgkmcnt<(RPK < 15 ? RPK : 15)>();
+    } else {
+      wait_lgkmcnt<0>();
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    const bf16x8 av = __builtin_shufflevector(aT[ring][0], aT[ring][1], 0, 1,
+                                              2, 3, 4, 5, 6, 7);
+#pragma unroll
+    for (int t = 0; t < NB; ++t) {
+      const bf16x8 bv = __builtin_shufflevector(
+          bT[ring][t][0], bT[ring][t][1], 0, 1, 2, 3, 4, 5, 6, 7);
+      acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc[t], 0, 0,
+                                                       0);
+    }
+  }
+}
+
+// Slab j ([WR*8 k][CT c][KS dx] floats, WK copies) -> dW: sum the copies in
+// order w = 0..WK-1 and add; consecutive threads add to consecutive addresses.
+template <class G>
+WN_DEVFN void patch_slab_drain(const float* slab, float* dW, int j, int kt0,
+                               int ct0, int dy_, int K, int C, int tid) {
+  constexpr int KS = G::KS, CT = G::CT, WK = G::WK, SLABN = G::SLABN;
+  for (int e = tid; e < SLABN; e += 256) {
+    float v = slab[e];
+#pragma unroll
+    for (int w = 1; w < WK; ++w) v += slab[w * SLABN + e];
+    const int kk = e / (CT * KS);
+    const int rem = e - kk * (CT * KS);
+    const int cc = rem / KS;
+    const int dx = rem - cc * KS;
+    const int k = kt0 + (kk >> 3) * 32 + j * 8 + (kk & 7);
+    const int cch = ct0 + cc;
+    if (k < K && cch < C)
+      atomicAdd(&dW[(((long)k * C + cch) * KS + dy_) * KS + dx], v);
+  }
+}
+
+// The patch kernels' body. ct0 / dy_: the block's channel tile and tap row.
+template <class G, class BF>
+WN_DEVFN void wgrad_patch_body(const bf16_t* __restrict__ dY,
+                               const bf16_t* __restrict__ X,
+                               float* __restrict__ dW, int N, int H, int W,
+                               int Cp, int Kp, int K, int C, int nSeg,
+                               const bf16_t* __restrict__ Zero16w, int ct0,
+                               int dy_) {
   static_assert(WN_MFMA_KMAP == 0, "wgrad staging assumes KMAP 0");
-  static_assert((BK == 32 || BK == 64) && (CT == 32 || CT == 64));
-  using G = PatchGeo<KS, BK, CT, CH>;
-  constexpr int PAD = KS / 2;
-  constexpr int WR = G::WR, WC = G::WC, WK = G::WK, KST = G::KST;
-  static_assert(CH % 16 == 0 && KST % WK == 0);
-  constexpr int KSTW = G::KSTW, NPX = G::NPX;
-  constexpr int ASLOTS = G::ASLOTS, BSLOTS = G::BSLOTS;
-  constexpr int SA = G::SA, SB = G::SB;
-  constexpr int ABYTES = G::ABYTES, BBYTES = G::BBYTES;
-  static_assert(pt_image_linear(CH, BK) && pt_image_linear(NPX, CT),
-                "glds slot order != image chunk order");
-  static_assert(pt_tr_conflict_free(BK, 12) &&
-                    pt_tr_conflict_free(CT, KS - 1 + 12),
-                "tr read bank conflict");
-  // last pixel row a tr read touches: last k-step, upper lane half, second
-  // 4-pixel read, row 3 (+ the last dx for the patch); the swizzle stays
-  // inside a row, so the row end bounds every lane address
-  static_assert((CH - 16 + 8 + 4 + 3 + 1) * BK * 2 <= ASLOTS * 16);
-  static_assert((CH - 16 + 8 + 4 + 3 + (KS - 1) + 1) * CT * 2 <= BSLOTS * 16);
+  static_assert(G::BK == 32 || G::BK == 64);
+  static_assert(G::CH % 16 == 0);
+  constexpr int KS = G::KS, BK = G::BK, CT = G::CT;
+  constexpr int WR = G::WR, WC = G::WC, SLABN = G::SLABN;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* lA = smem;               // 2 x ABYTES
-  char* lB = smem + 2 * ABYTES;  // 2 x BBYTES
+  char* lA = smem;                  // 2 x ABYTES
+  char* lB = smem + 2 * G::ABYTES;  // 2 x BBYTES
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -544,139 +730,33 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_patch(
   const int wr = (wid % (WR * WC)) / WC;
   const int wc = wid % WC;
   const int kt0 = blockIdx.x * BK;
-  const int ct0 = (blockIdx.y / KS) * CT;
-  const int dy_ = blockIdx.y % KS;
 
-  // output rows whose input row oy + dy - PAD lies inside the image
-  const int oyLo = max(0, PAD - dy_);
-  const int Hv = min(H, H + PAD - dy_) - oyLo;
-  if (Hv <= 0) return;  // block-uniform, nothing staged or read yet
-  const int total = N * Hv * nSeg;
-  const int per = (total + (int)gridDim.z - 1) / (int)gridDim.z;
-  const int c0 = blockIdx.z * per;
-  const int c1 = min(total, c0 + per);
-  if (c0 >= c1) return;  // block-uniform
-  int n = c0 / (Hv * nSeg);
-  int oyv = (c0 - n * Hv * nSeg) / nSeg;
-  int seg = c0 - (n * Hv + oyv) * nSeg;
+  PatchOwner own;
+  if (!own.init(N, H, KS / 2, dy_, nSeg)) return;
+  PatchStager<G> stage{dY, X, Zero16w, lA, lB, H, W, Kp, Cp, kt0, ct0, dy_,
+                       tid};
+  stage.init_slots();
 
-  // ---- static slot geometry (slot -> pixel row, source chunk) ----
-  int aPix[SA], aCh[SA], bPix[SB], bCh[SB];
+  f32x16 acc[BF::NB];
 #pragma unroll
-  for (int s = 0; s < SA; ++s) {
-    const int sg = tid + s * 256;
-    aPix[s] = (sg < ASLOTS) ? pt_slot_pix(sg, BK) : (1 << 28);  // -> zero
-    aCh[s] = pt_slot_chunk(sg, BK) * 8;
-  }
-#pragma unroll
-  for (int s = 0; s < SB; ++s) {
-    const int sg = tid + s * 256;
-    bPix[s] = (sg < BSLOTS) ? pt_slot_pix(sg, CT) - PAD : (1 << 28);
-    bCh[s] = pt_slot_chunk(sg, CT) * 8;
-  }
-
-  auto stage = [&](int buf, int n_, int oy, int sg_) {
-    const int ox0 = sg_ * CH;
-    const long rowm = ((long)n_ * H + oy) * W;
-    const long rowx = ((long)n_ * H + oy + dy_ - PAD) * W;
-#pragma unroll
-    for (int s = 0; s < SA; ++s) {
-      const bf16_t* src = Zero16w;
-      const int ox = ox0 + aPix[s];
-      if (ox < W) src = dY + (rowm + ox) * Kp + kt0 + aCh[s];
-      __builtin_amdgcn_global_load_lds(
-          src, lA + buf * ABYTES + (tid + s * 256) * 16, 16, 0, 0);
-    }
-#pragma unroll
-    for (int s = 0; s < SB; ++s) {
-      const bf16_t* src = Zero16w;
-      const int ix = ox0 + bPix[s];
-      if (ix >= 0 && ix < W) src = X + (rowx + ix) * Cp + ct0 + bCh[s];
-      __builtin_amdgcn_global_load_lds(
-          src, lB + buf * BBYTES + (tid + s * 256) * 16, 16, 0, 0);
-    }
-  };
-
-  f32x16 acc[KS];
-#pragma unroll
-  for (int t = 0; t < KS; ++t)
+  for (int t = 0; t < BF::NB; ++t)
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
 
-  // per-lane tr-read bases. Lane l reads column (l&31) of its 32-wide
-  // block: 16-column half (l>>4)&1, reduction pixels (l>>5)*8 + 4h + e;
-  // inside the 16-lane group, lane 4q+p addresses row q, columns 4p..4p+3.
-  // The pixel of a read is rowl + (16*kst + 4h + dx): only (q + dx) & 2
-  // feeds the swizzle, so 4 B bases (dx & 3) cover every shift.
-  const int q = (lane & 15) >> 2;
-  const int rowl = wk * 16 + (lane >> 5) * 8 + q;
-  const int acol2 = (wr * 32 + ((lane >> 4) & 1) * 16 + (lane & 3) * 4) * 2;
-  const int bcol2 = (wc * 32 + ((lane >> 4) & 1) * 16 + (lane & 3) * 4) * 2;
-  const unsigned aB0 = (unsigned)(unsigned long long)lA +
-                       (unsigned)(rowl * BK * 2 + (acol2 ^ pt_swz(q, BK)));
-  unsigned bB0[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-    bB0[c] = (unsigned)(unsigned long long)lB +
-             (unsigned)(rowl * CT * 2 + (bcol2 ^ pt_swz(q + c, CT)));
+  const PatchLane L(lane, wk);
+  const unsigned aB0 = patch_a_base<BK>(lA, L, lane, wr);
+  const BF bf0(lB, L, lane, wc);
 
   int buf = 0;
-  stage(0, n, oyLo + oyv, seg);
+  stage(0, own.n, own.oy(), own.seg);
   __syncthreads();  // drains the DMA (vmcnt 0) + barrier
-  for (int c = c0; c < c1; ++c) {
-    if (++seg == nSeg) {
-      seg = 0;
-      if (++oyv == Hv) { oyv = 0; ++n; }
-    }
-    if (c + 1 < c1) stage(buf ^ 1, n, oyLo + oyv, seg);  // DMA under the math
-    const unsigned aB = aB0 + (unsigned)(buf * ABYTES);
-    unsigned bB[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) bB[i] = bB0[i] + (unsigned)(buf * BBYTES);
-
-    constexpr int RPK = 2 + 2 * KS;  // tr reads per k-step
-    bf16x4 aT[2][2], bT[2][KS][2];   // 2-deep k-step ring
-    auto rdk = [&](int i, int ring) {
-      const int p0 = i * WK * 16;  // first pixel of this wave's i-th k-step
-      aT[ring][0] = ds_tr16(aB + (unsigned)(p0 * BK * 2));
-      aT[ring][1] = ds_tr16(aB + (unsigned)((p0 + 4) * BK * 2));
-#pragma unroll
-      for (int dx = 0; dx < KS; ++dx) {
-        bT[ring][dx][0] =
-            ds_tr16(bB[dx & 3] + (unsigned)((p0 + dx) * CT * 2));
-        bT[ring][dx][1] =
-            ds_tr16(bB[dx & 3] + (unsigned)((p0 + 4 + dx) * CT * 2));
-      }
-    };
-    rdk(0, 0);
-#pragma unroll
-    for (int i = 0; i < KSTW; ++i) {
-      const int ring = i & 1;
-      if (i + 1 < KSTW) {
-        rdk(i + 1, ring ^ 1);
-        // wait for THIS k-step's reads only (lgkmcnt saturates at 15, so
-        // KS=7's 16 in-flight reads wait for one more than needed)
-        if constexpr (RPK == 8)
-          asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
-        else if constexpr (RPK == 12)
-          asm volatile("s_waitcnt lgkmcnt(12)" ::: "memory");
-        else
-          asm volatile("s_waitcnt lgkmcnt(15)" ::: "memory");
-      } else {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      const bf16x8 av = __builtin_shufflevector(
-          aT[ring][0], aT[ring][1], 0, 1, 2, 3, 4, 5, 6, 7);
-#pragma unroll
-      for (int dx = 0; dx < KS; ++dx) {
-        const bf16x8 bv = __builtin_shufflevector(
-            bT[ring][dx][0], bT[ring][dx][1], 0, 1, 2, 3, 4, 5, 6, 7);
-        acc[dx] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc[dx],
-                                                          0, 0, 0);
-      }
-    }
-    if (c + 1 < c1) __syncthreads();  // drains DMA + joins waves
+  for (int c = own.c0; c < own.c1; ++c) {
+    own.advance(nSeg);
+    if (c + 1 < own.c1)
+      stage(buf ^ 1, own.n, own.oy(), own.seg);  // DMA under the math
+    patch_chunk_mma<G>(acc, aB0 + (unsigned)(buf * G::ABYTES),
+                       bf0.at((unsigned)(buf * G::BBYTES)));
+    if (c + 1 < own.c1) __syncthreads();  // drains DMA + joins waves
     buf ^= 1;
   }
 
@@ -686,11 +766,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_patch(
   //      own cache line (c stride = KS*KS floats). So the tile goes through
   //      LDS in 4 slabs of WR*8 k rows laid out [k][c][dx] — dW's own order
   //      for one dy — the WK k-step waves' partial sums are added on the
-  //      way out, and consecutive lanes add to consecutive addresses. ----
-  constexpr int SLABN = G::SLABN;  // floats per slab copy
-  // all WK slab copies: 4096*KS bytes; LDS_BYTES is the larger of this and
-  // the staging buffers
-  static_assert(WK * SLABN * 4 == 4096 * KS);
+  //      way out, and consecutive lanes add to consecutive addresses. The
+  //      WK slab copies reuse the staging buffers (LDS_BYTES covers both). ----
   float* slab = reinterpret_cast<float*>(smem);
   __syncthreads();  // every wave is past its last tr read; no DMA in flight
 #pragma unroll
@@ -698,28 +775,42 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_patch(
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) {
       const int kk = wr * 8 + rr + 4 * (lane >> 5);
-      float* dst =
-          slab + wk * SLABN + (kk * CT + wc * 32 + (lane & 31)) * KS;
-#pragma unroll
-      for (int dx = 0; dx < KS; ++dx) dst[dx] = acc[dx][4 * j + rr];
+      bf0.scatter(slab + wk * SLABN + kk * CT * KS, acc, 4 * j + rr);
     }
     __syncthreads();
-    for (int e = tid; e < SLABN; e += 256) {
-      float v = slab[e];
-#pragma unroll
-      for (int w = 1; w < WK; ++w) v += slab[w * SLABN + e];
-      const int kk = e / (CT * KS);
-      const int rem = e - kk * (CT * KS);
-      const int cc = rem / KS;
-      const int dx = rem - cc * KS;
-      const int k = kt0 + (kk >> 3) * 32 + j * 8 + (kk & 7);
-      const int cch = ct0 + cc;
-      if (k < K && cch < C)
-        atomicAdd(&dW[(((long)k * C + cch) * KS + dy_) * KS + dx], v);
-    }
+    patch_slab_drain<G>(slab, dW, j, kt0, ct0, dy_, K, C, tid);
     __syncthreads();
   }
 }
+
+template <int KS, int BK, int CT, int CH>
+__global__ __launch_bounds__(256, 2) void k_conv_wgrad_patch(
+    const bf16_t* __restrict__ dY,  // (N,H,W,Kp)
+    const bf16_t* __restrict__ X,   // (N,H,W,Cp)
+    float* __restrict__ dW,         // (K, C, KS, KS) fp32, accumulated into
+    int N, int H, int W, int Cp, int Kp, int K, int C, int nSeg,
+    const bf16_t* __restrict__ Zero16w) {
+  using G = PatchGeo<KS, BK, CT, CH>;
+  static_assert(CT == 32 || CT == 64);
+  static_assert(G::KST % G::WK == 0 && G::PXA == CH);
+  static_assert(PtImage::linear(CH, BK) && PtImage::linear(G::NPX, CT),
+                "glds slot order != image chunk order");
+  static_assert(pt_tr_conflict_free(BK, 12) &&
+                    pt_tr_conflict_free(CT, KS - 1 + 12),
+                "tr read bank conflict");
+  // last pixel row a tr read touches: last k-step, upper lane half, second
+  // 4-pixel read, row 3 (+ the last dx for the patch); the swizzle stays
+  // inside a row, so the row end bounds every lane address
+  static_assert((CH - 16 + 8 + 4 + 3 + 1) * BK * 2 <= G::ASLOTS * 16);
+  static_assert((CH - 16 + 8 + 4 + 3 + (KS - 1) + 1) * CT * 2 <=
+                G::BSLOTS * 16);
+  // all WK slab copies: 4096*KS bytes
+  static_assert(G::WK * G::SLABN * 4 == 4096 * KS);
+  wgrad_patch_body<G, PatchTapFrags<KS, CT>>(
+      dY, X, dW, N, H, W, Cp, Kp, K, C, nSeg, Zero16w,
+      (int)(blockIdx.y / KS) * CT, (int)(blockIdx.y % KS));
+}
+
 
 // ---------------------------------------------------------------------------
 // Patch weight gradient for Cp = 16 (the 12->128 / 6->32 input convs): two
@@ -761,23 +852,38 @@ constexpr bool pt_tr_pair_conflict_free(int maxShift) {
   return true;
 }
 
+// 16-channel tile: the patch is the chunk plus the 2*PAD halo and the
+// phantom pixel
 template <int KS, int BK, int CH>
-struct Patch16Geo {
-  static constexpr int NT = (KS + 1) / 2;  // tap-pair accumulators
-  static constexpr int WR = BK / 32, WK = 4 / WR;
-  static constexpr int KST = CH / 16;
-  static constexpr int KSTW = (KST + WK - 1) / WK;  // k-steps per wave
-  static constexpr int PXA = KSTW * WK * 16;  // pixel rows the waves walk
-  static constexpr int NPX = CH + KS;         // 2*PAD halo + phantom pixel
-  static constexpr int ACPR = BK / 8, BCPR = 2;  // 16 B chunks per row
-  static constexpr int ASLOTS = CH * ACPR, BSLOTS = NPX * BCPR;
-  static constexpr int SA = (PXA * ACPR + 255) / 256;
-  static constexpr int SB = ((PXA + KS) * BCPR + 255) / 256;
-  static constexpr int ABYTES = SA * 256 * 16, BBYTES = SB * 256 * 16;
-  static constexpr int SLABN = WR * 8 * 16 * KS;  // floats per slab copy
-  static constexpr int LDS_BYTES =
-      2 * (ABYTES + BBYTES) > WK * SLABN * 4 ? 2 * (ABYTES + BBYTES)
-                                             : WK * SLABN * 4;
+struct Patch16Geo : PatchGeoBase<KS, BK, 16, CH, CH + KS> {};
+
+// B fragments of the 16-channel patch: fragment t is the tap pair (2t, 2t+1),
+// the read moved 2t pixel rows. 32 B rows carry no swizzle, so one base
+// serves every shift; the 16-column half hb is one whole pixel row further on.
+template <int KS>
+struct PatchPairFrags {
+  static constexpr int NB = (KS + 1) / 2, CT = 16;  // tap-pair accumulators
+  unsigned b;
+  int col, hb;  // D column c' of the lane: channel c' & 15, pair half c' >> 4
+  WN_DEVFN PatchPairFrags(const char* lB, PatchLane L, int lane, int)
+      : b((unsigned)(unsigned long long)lB +
+          (unsigned)((L.rowl + L.hb) * CT * 2 + (lane & 3) * 8)),
+        col(lane & 15), hb(L.hb) {}
+  WN_DEVFN PatchPairFrags at(unsigned bufOff) const {
+    PatchPairFrags f = *this;
+    f.b += bufOff;
+    return f;
+  }
+  WN_DEVFN unsigned addr(int t, int p) const {
+    return b + (unsigned)((p + 2 * t) * CT * 2);
+  }
+  // accumulator t holds taps 2t + hb; the phantom tap dx = KS is not written
+  WN_DEVFN void scatter(float* row, const f32x16 (&acc)[NB], int r) const {
+    float* dst = row + col * KS + hb;
+#pragma unroll
+    for (int t = 0; t < NB; ++t)
+      if (2 * t + 1 < KS || hb == 0) dst[2 * t] = acc[t][r];
+  }
 };
 
 template <int KS, int BK, int CH>
@@ -787,18 +893,9 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_patch16(
     float* __restrict__ dW,         // (K, C, KS, KS) fp32, accumulated into
     int N, int H, int W, int Kp, int K, int C, int nSeg,
     const bf16_t* __restrict__ Zero16w) {
-  static_assert(WN_MFMA_KMAP == 0, "wgrad staging assumes KMAP 0");
-  static_assert(BK == 32 || BK == 64);
-  static_assert(CH % 16 == 0);
   using G = Patch16Geo<KS, BK, CH>;
-  constexpr int CT = 16;
-  constexpr int PAD = KS / 2;
-  constexpr int NT = G::NT, WR = G::WR, WK = G::WK, KSTW = G::KSTW;
-  constexpr int PXA = G::PXA, NPX = G::NPX;
-  constexpr int ASLOTS = G::ASLOTS, BSLOTS = G::BSLOTS;
-  constexpr int SA = G::SA, SB = G::SB;
-  constexpr int ABYTES = G::ABYTES, BBYTES = G::BBYTES;
-  static_assert(pt_image_linear(CH, BK) && pt_image_linear(NPX, CT),
+  constexpr int CT = G::CT;
+  static_assert(PtImage::linear(CH, BK) && PtImage::linear(G::NPX, CT),
                 "glds slot order != image chunk order");
   static_assert(pt_tr_conflict_free(BK, 12) &&
                     pt_tr_pair_conflict_free(KS - 1 + 12),
@@ -806,177 +903,14 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_patch16(
   // last pixel row a tr read of a real k-step touches: last k-step, upper
   // lane half, second 4-pixel read, row 3 (+ the last shift and the pair's
   // second pixel for the patch) — inside the staged, defined image
-  static_assert((CH - 16 + 8 + 4 + 3 + 1) * BK * 2 <= ASLOTS * 16);
+  static_assert((CH - 16 + 8 + 4 + 3 + 1) * BK * 2 <= G::ASLOTS * 16);
   static_assert((CH - 16 + 8 + 4 + 3 + (KS - 1) + 1 + 1) * CT * 2 <=
-                BSLOTS * 16);
+                G::BSLOTS * 16);
   // the same for the padded k-steps: inside the zero-sourced surplus slots
-  static_assert(PXA * BK * 2 <= ABYTES && (PXA + KS) * CT * 2 <= BBYTES);
-
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* lA = smem;               // 2 x ABYTES
-  char* lB = smem + 2 * ABYTES;  // 2 x BBYTES
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int wk = wid / WR;
-  const int wr = wid % WR;
-  const int kt0 = blockIdx.x * BK;
-  const int dy_ = blockIdx.y;
-
-  // output rows whose input row oy + dy - PAD lies inside the image
-  const int oyLo = max(0, PAD - dy_);
-  const int Hv = min(H, H + PAD - dy_) - oyLo;
-  if (Hv <= 0) return;  // block-uniform, nothing staged or read yet
-  const int total = N * Hv * nSeg;
-  const int per = (total + (int)gridDim.z - 1) / (int)gridDim.z;
-  const int c0 = blockIdx.z * per;
-  const int c1 = min(total, c0 + per);
-  if (c0 >= c1) return;  // block-uniform
-  int n = c0 / (Hv * nSeg);
-  int oyv = (c0 - n * Hv * nSeg) / nSeg;
-  int seg = c0 - (n * Hv + oyv) * nSeg;
-
-  // ---- static slot geometry (slot -> pixel row, source chunk) ----
-  int aPix[SA], aCh[SA], bPix[SB], bCh[SB];
-#pragma unroll
-  for (int s = 0; s < SA; ++s) {
-    const int sg = tid + s * 256;
-    aPix[s] = (sg < ASLOTS) ? pt_slot_pix(sg, BK) : (1 << 28);  // -> zero
-    aCh[s] = pt_slot_chunk(sg, BK) * 8;
-  }
-#pragma unroll
-  for (int s = 0; s < SB; ++s) {
-    const int sg = tid + s * 256;
-    bPix[s] = (sg < BSLOTS) ? pt_slot_pix(sg, CT) - PAD : (1 << 28);
-    bCh[s] = pt_slot_chunk(sg, CT) * 8;
-  }
-
-  auto stage = [&](int buf, int n_, int oy, int sg_) {
-    const int ox0 = sg_ * CH;
-    const long rowm = ((long)n_ * H + oy) * W;
-    const long rowx = ((long)n_ * H + oy + dy_ - PAD) * W;
-#pragma unroll
-    for (int s = 0; s < SA; ++s) {
-      const bf16_t* src = Zero16w;
-      const int ox = ox0 + aPix[s];
-      if (ox < W) src = dY + (rowm + ox) * Kp + kt0 + aCh[s];
-      __builtin_amdgcn_global_load_lds(
-          src, lA + buf * ABYTES + (tid + s * 256) * 16, 16, 0, 0);
-    }
-#pragma unroll
-    for (int s = 0; s < SB; ++s) {
-      const bf16_t* src = Zero16w;
-      const int ix = ox0 + bPix[s];
-      if (ix >= 0 && ix < W) src = X + (rowx + ix) * CT + bCh[s];
-      __builtin_amdgcn_global_load_lds(
-          src, lB + buf * BBYTES + (tid + s * 256) * 16, 16, 0, 0);
-    }
-  };
-
-  f32x16 acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
-
-  // per-lane tr-read bases, as in k_conv_wgrad_patch; for the patch the
-  // 16-column half (l>>4)&1 is one whole 32-byte pixel row further on
-  const int q = (lane & 15) >> 2;
-  const int hb = (lane >> 4) & 1;
-  const int rowl = wk * 16 + (lane >> 5) * 8 + q;
-  const int acol2 = (wr * 32 + hb * 16 + (lane & 3) * 4) * 2;
-  const unsigned aB0 = (unsigned)(unsigned long long)lA +
-                       (unsigned)(rowl * BK * 2 + (acol2 ^ pt_swz(q, BK)));
-  const unsigned bB0 = (unsigned)(unsigned long long)lB +
-                       (unsigned)((rowl + hb) * CT * 2 + (lane & 3) * 8);
-
-  int buf = 0;
-  stage(0, n, oyLo + oyv, seg);
-  __syncthreads();  // drains the DMA (vmcnt 0) + barrier
-  for (int c = c0; c < c1; ++c) {
-    if (++seg == nSeg) {
-      seg = 0;
-      if (++oyv == Hv) { oyv = 0; ++n; }
-    }
-    if (c + 1 < c1) stage(buf ^ 1, n, oyLo + oyv, seg);  // DMA under the math
-    const unsigned aB = aB0 + (unsigned)(buf * ABYTES);
-    const unsigned bB = bB0 + (unsigned)(buf * BBYTES);
-
-    constexpr int RPK = 2 + 2 * NT;  // tr reads per k-step (6, 8 or 10)
-    bf16x4 aT[2][2], bT[2][NT][2];   // 2-deep k-step ring
-    auto rdk = [&](int i, int ring) {
-      const int p0 = i * WK * 16;  // first pixel of this wave's i-th k-step
-      aT[ring][0] = ds_tr16(aB + (unsigned)(p0 * BK * 2));
-      aT[ring][1] = ds_tr16(aB + (unsigned)((p0 + 4) * BK * 2));
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        bT[ring][t][0] = ds_tr16(bB + (unsigned)((p0 + 2 * t) * CT * 2));
-        bT[ring][t][1] = ds_tr16(bB + (unsigned)((p0 + 4 + 2 * t) * CT * 2));
-      }
-    };
-    rdk(0, 0);
-#pragma unroll
-    for (int i = 0; i < KSTW; ++i) {
-      const int ring = i & 1;
-      if (i + 1 < KSTW) {
-        rdk(i + 1, ring ^ 1);
-        // wait for THIS k-step's reads only
-        if constexpr (RPK == 6)
-          asm volatile("s_waitcnt lgkmcnt(6)" ::: "memory");
-        else if constexpr (RPK == 8)
-          asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
-        else
-          asm volatile("s_waitcnt lgkmcnt(10)" ::: "memory");
-      } else {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      const bf16x8 av = __builtin_shufflevector(
-          aT[ring][0], aT[ring][1], 0, 1, 2, 3, 4, 5, 6, 7);
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        const bf16x8 bv = __builtin_shufflevector(
-            bT[ring][t][0], bT[ring][t][1], 0, 1, 2, 3, 4, 5, 6, 7);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc[t],
-                                                         0, 0, 0);
-      }
-    }
-    if (c + 1 < c1) __syncthreads();  // drains DMA + joins waves
-    buf ^= 1;
-  }
-
-  // ---- epilogue: the slab scheme of k_conv_wgrad_patch, [k][c][dx] with
-  //      16 channels. D column c' of accumulator t is tap 2t + (c' >> 4),
-  //      channel c' & 15; the phantom tap dx = KS is not written. ----
-  constexpr int SLABN = G::SLABN;
-  float* slab = reinterpret_cast<float*>(smem);
-  __syncthreads();  // every wave is past its last tr read; no DMA in flight
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-      const int kk = wr * 8 + rr + 4 * (lane >> 5);
-      float* dst = slab + wk * SLABN + (kk * CT + (lane & 15)) * KS + hb;
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-        if (2 * t + 1 < KS || hb == 0) dst[2 * t] = acc[t][4 * j + rr];
-    }
-    __syncthreads();
-    for (int e = tid; e < SLABN; e += 256) {
-      float v = slab[e];
-#pragma unroll
-      for (int w = 1; w < WK; ++w) v += slab[w * SLABN + e];
-      const int kk = e / (CT * KS);
-      const int rem = e - kk * (CT * KS);
-      const int cc = rem / KS;
-      const int dx = rem - cc * KS;
-      const int k = kt0 + (kk >> 3) * 32 + j * 8 + (kk & 7);
-      if (k < K && cc < C)
-        atomicAdd(&dW[(((long)k * C + cc) * KS + dy_) * KS + dx], v);
-    }
-    __syncthreads();
-  }
+  static_assert(G::PXA * BK * 2 <= G::ABYTES &&
+                (G::PXA + KS) * CT * 2 <= G::BBYTES);
+  wgrad_patch_body<G, PatchPairFrags<KS>>(dY, X, dW, N, H, W, CT, Kp, K, C,
+                                          nSeg, Zero16w, 0, (int)blockIdx.y);
 }
 
 // ---------------------------------------------------------------------------
@@ -988,6 +922,13 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_patch16(
 // sharing the octet, then atomically adds into the fp32 dW.
 // ---------------------------------------------------------------------------
 
+// reduction scratch: one row of 256 threads per (k, e) partial sum
+template <int KMAX>
+struct SmallKGeo {
+  static constexpr int RED_ROWS = KMAX * 8;
+  static constexpr int LDS_BYTES = RED_ROWS * 256 * (int)sizeof(float);
+};
+
 template <int KMAX, int U>
 __global__ __launch_bounds__(256, 4) void k_wgrad_smallk(
     const bf16_t* __restrict__ dY,  // (M, Kp)
@@ -997,7 +938,8 @@ __global__ __launch_bounds__(256, 4) void k_wgrad_smallk(
     int msplit, unsigned long long mulHW, unsigned long long mulW) {
   static_assert(KMAX == 4, "the dY row is read as one 8-byte vector");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* red = reinterpret_cast<float*>(smem);  // [256][KMAX*8]
+  float* red = reinterpret_cast<float*>(smem);  // [RED_ROWS][256]
+  constexpr int RED_ROWS = SmallKGeo<KMAX>::RED_ROWS;
   const int PAD = KS / 2;
   const long M = (long)N * H * W;
   const int HW = H * W;
@@ -1064,13 +1006,13 @@ __global__ __launch_bounds__(256, 4) void k_wgrad_smallk(
   for (int s = MR / 2; s > 0; s >>= 1) {
     if (mr < s) {
 #pragma unroll
-      for (int j = 0; j < KMAX * 8; ++j)
+      for (int j = 0; j < RED_ROWS; ++j)
         red[j * 256 + tid] += red[j * 256 + tid + s * CG];
     }
     __syncthreads();
   }
   // row j of red now holds its CG octet sums in columns 0..CG-1
-  for (int t = tid; t < KMAX * 8 * CG; t += 256) {
+  for (int t = tid; t < RED_ROWS * CG; t += 256) {
     const int j = t / CG, g = t - j * CG;
     const int k = j >> 3, c = g * 8 + (j & 7);
     if (k < K && c < C)
@@ -1102,7 +1044,7 @@ __global__ void k_probe_tr(float* __restrict__ out /* [64][2][4] */) {
     const unsigned b = base0 + (unsigned)(f * TR_KBS) * 2;
     bf16x4 lo = ds_tr16(b);
     bf16x4 hi = ds_tr16(b + TR_MBS * 2);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkmcnt<0>();
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       out[(lane * 2 + f) * 8 + j] = bf2f(lo[j]);
@@ -1122,7 +1064,7 @@ __global__ void k_probe_tr_raw(float* __restrict__ out /* [64][4] */) {
   const unsigned addr =
       (unsigned)(unsigned long long)img + (unsigned)lane * 8;
   bf16x4 v = ds_tr16(addr);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  wait_lgkmcnt<0>();
 #pragma unroll
   for (int j = 0; j < 4; ++j) out[lane * 4 + j] = bf2f(v[j]);
 }
@@ -1159,11 +1101,17 @@ at::Tensor probe_tr_raw() {
 // a plain fp32 partial slab Part[blockIdx.y][Kp] (no atomics — dB is a few
 // cache lines and msplit*K atomics serialize on them; measured 2.2 ms ->
 // slabs + the tiny reduce below). Grid: (ceil(ngrp/KGR), msplit).
+struct BiasGradGeo {
+  static constexpr int RED_COLS = 8;  // fp32 partials per thread
+  static constexpr int LDS_BYTES = 256 * RED_COLS * (int)sizeof(float);
+};
+
 __global__ void k_bias_grad(const bf16_t* __restrict__ dY,
                             float* __restrict__ Part, long M, int Kp,
                             int msplit) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* red = reinterpret_cast<float*>(smem);  // [256][8] fp32
+  float* red = reinterpret_cast<float*>(smem);  // [256][RED_COLS] fp32
+  constexpr int RED_COLS = BiasGradGeo::RED_COLS;
   const int ngrp = Kp >> 3;                  // 8-wide k-groups in Kp
   const int KGR = min(ngrp, 32);             // k-groups per block
   const int MR = 256 / KGR;                  // m-rows strided per block
@@ -1183,14 +1131,14 @@ __global__ void k_bias_grad(const bf16_t* __restrict__ dY,
     }
   }
 #pragma unroll
-  for (int e = 0; e < 8; ++e) red[threadIdx.x * 8 + e] = acc[e];
+  for (int e = 0; e < 8; ++e) red[threadIdx.x * RED_COLS + e] = acc[e];
   __syncthreads();
   // tree-reduce over the MR rows that share this thread's k-group
   if (mr == 0 && k0 < Kp) {
 #pragma unroll 1
     for (int r = 1; r < MR; ++r)
 #pragma unroll
-      for (int e = 0; e < 8; ++e) acc[e] += red[(r * KGR + kg) * 8 + e];
+      for (int e = 0; e < 8; ++e) acc[e] += red[(r * KGR + kg) * RED_COLS + e];
     *reinterpret_cast<f32x4*>(&Part[(long)blockIdx.y * Kp + k0]) =
         f32x4{acc[0], acc[1], acc[2], acc[3]};
     *reinterpret_cast<f32x4*>(&Part[(long)blockIdx.y * Kp + k0 + 4]) =
@@ -1229,7 +1177,11 @@ constexpr int WGRAD_SMALLK_BLOCKS = 768;
 constexpr double WGRAD_SMALLK_BLOCKS_K = 0.17;
 constexpr int WGRAD_SMALLK_U = 4;
 
-// k_conv_wgrad_patch16 split-m rule: blocks = K * sqrt(work/tile), capped.
+// Patch kernels' split-m rule: blocks = K * sqrt(work/tile), capped. The
+// patch16 tile (BK*16*KS atomics) is 4x smaller than 64x64, so more blocks
+// pay.
+constexpr double WGRAD_PATCH_BLOCKS_K = 110.0;
+constexpr int WGRAD_PATCH_BLOCKS_MAX = 768;
 constexpr double WGRAD_PATCH16_BLOCKS_K = 80.0;
 constexpr int WGRAD_PATCH16_BLOCKS_MAX = 1024;
 
@@ -1248,46 +1200,28 @@ inline int patch_split(double work, int tile, int gxgy, double k, int cap,
   return (int)std::min<long>(split, maxChunks);
 }
 
-template <int KS, int BKCT, int CH>
-void launch_wgrad_patch_t(const at::Tensor& dy, const at::Tensor& x,
+// Launch of a patch kernel with tile constants G; blocks_k / blocks_max are
+// its patch_split constants. cp is the kernel's Cp argument:
+// k_conv_wgrad_patch takes one, k_conv_wgrad_patch16 (Cp = 16) has none.
+template <class G, class Kern, class... CpArg>
+void launch_wgrad_patch_t(Kern kern, double blocks_k, int blocks_max,
+                          const at::Tensor& dy, const at::Tensor& x,
                           at::Tensor& dw, const bf16_t* zero16,
-                          hipStream_t stream) {
-  using G = PatchGeo<KS, BKCT, BKCT, CH>;
+                          hipStream_t stream, CpArg... cp) {
   const int N = x.size(0), H = x.size(1), W = x.size(2), Cp = x.size(3);
   const int Kp = dy.size(3);
   const int K = dw.size(0), C = dw.size(1);
-  const int nSeg = (W + CH - 1) / CH;
-  const int gx = Kp / BKCT, gy = (Cp / BKCT) * KS;
-  const double work = (double)gx * gy * N * H * nSeg * (CH / 16);
-  const int split = patch_split(work, BKCT * BKCT * KS, gx * gy, 110.0, 768,
-                                (long)N * H * nSeg);
-  hipLaunchKernelGGL((k_conv_wgrad_patch<KS, BKCT, BKCT, CH>),
-                     dim3(gx, gy, split), dim3(256), (size_t)G::LDS_BYTES,
-                     stream, (const bf16_t*)dy.data_ptr(),
+  const int nSeg = (W + G::CH - 1) / G::CH;
+  const int gx = Kp / G::BK, gy = (Cp / G::CT) * G::KS;
+  const double work = (double)gx * gy * N * H * nSeg * (G::CH / 16);
+  // a block's atomics: its BK x CT tile of one dy row
+  const int split = patch_split(work, G::BK * G::CT * G::KS, gx * gy, blocks_k,
+                                blocks_max, (long)N * H * nSeg);
+  hipLaunchKernelGGL(kern, dim3(gx, gy, split), dim3(256),
+                     (size_t)G::LDS_BYTES, stream,
+                     (const bf16_t*)dy.data_ptr(),
                      (const bf16_t*)x.data_ptr(), dw.data_ptr<float>(), N, H,
-                     W, Cp, Kp, K, C, nSeg, zero16);
-}
-
-template <int KS, int BK, int CH>
-void launch_wgrad_patch16_t(const at::Tensor& dy, const at::Tensor& x,
-                            at::Tensor& dw, const bf16_t* zero16,
-                            hipStream_t stream) {
-  using G = Patch16Geo<KS, BK, CH>;
-  const int N = x.size(0), H = x.size(1), W = x.size(2);
-  const int Kp = dy.size(3);
-  const int K = dw.size(0), C = dw.size(1);
-  const int nSeg = (W + CH - 1) / CH;
-  const int gx = Kp / BK, gy = KS;
-  // the tile (BK*16*KS atomics) is 4x smaller than 64x64, so more blocks pay
-  const double work = (double)gx * gy * N * H * nSeg * (CH / 16);
-  const int split =
-      patch_split(work, BK * 16 * KS, gx * gy, WGRAD_PATCH16_BLOCKS_K,
-                  WGRAD_PATCH16_BLOCKS_MAX, (long)N * H * nSeg);
-  hipLaunchKernelGGL((k_conv_wgrad_patch16<KS, BK, CH>),
-                     dim3(gx, gy, split), dim3(256), (size_t)G::LDS_BYTES,
-                     stream, (const bf16_t*)dy.data_ptr(),
-                     (const bf16_t*)x.data_ptr(), dw.data_ptr<float>(), N, H,
-                     W, Kp, K, C, nSeg, zero16);
+                     W, cp..., Kp, K, C, nSeg, zero16);
 }
 
 // cls: 64 (Cp and Kp multiples of 64), 32 (32 -> 32) or 16 (Cp = 16).
@@ -1308,19 +1242,26 @@ void launch_wgrad_patch(const at::Tensor& dy, const at::Tensor& x,
     if (force_ch == 64 || force_ch == 112) ch = force_ch;
   }
   const int bk16 = dy.size(3) == 32 ? 32 : 64;  // cls 16: Kp = 32 or n*64
+  const int Cp = x.size(3);
   dispatch_int<3, 5, 7>(ks, "kernel size", [&](auto ks_const) {
     constexpr int KSV = decltype(ks_const)::value;
     dispatch_int<64, 112>(ch, "patch chunk length", [&](auto ch_const) {
       constexpr int CHV = decltype(ch_const)::value;
       if (cls == 16)
         dispatch_int<32, 64>(bk16, "patch16 k tile", [&](auto bk_const) {
-          launch_wgrad_patch16_t<KSV, decltype(bk_const)::value, CHV>(
-              dy, x, dw, zero16, stream);
+          constexpr int BKV = decltype(bk_const)::value;
+          launch_wgrad_patch_t<Patch16Geo<KSV, BKV, CHV>>(
+              k_conv_wgrad_patch16<KSV, BKV, CHV>, WGRAD_PATCH16_BLOCKS_K,
+              WGRAD_PATCH16_BLOCKS_MAX, dy, x, dw, zero16, stream);
         });
       else if (cls == 32)
-        launch_wgrad_patch_t<KSV, 32, 64>(dy, x, dw, zero16, stream);
+        launch_wgrad_patch_t<PatchGeo<KSV, 32, 32, 64>>(
+            k_conv_wgrad_patch<KSV, 32, 32, 64>, WGRAD_PATCH_BLOCKS_K,
+            WGRAD_PATCH_BLOCKS_MAX, dy, x, dw, zero16, stream, Cp);
       else
-        launch_wgrad_patch_t<KSV, 64, CHV>(dy, x, dw, zero16, stream);
+        launch_wgrad_patch_t<PatchGeo<KSV, 64, 64, CHV>>(
+            k_conv_wgrad_patch<KSV, 64, 64, CHV>, WGRAD_PATCH_BLOCKS_K,
+            WGRAD_PATCH_BLOCKS_MAX, dy, x, dw, zero16, stream, Cp);
     });
   });
 }
@@ -1359,7 +1300,7 @@ void conv2d_wgrad(const at::Tensor& dy, const at::Tensor& x, at::Tensor& dw,
     dispatch_int<1, 2, 4, 6>(unroll, "WN_WGRAD_SMALLK_U", [&](auto u_const) {
       constexpr int UV = decltype(u_const)::value;
       hipLaunchKernelGGL((k_wgrad_smallk<4, UV>), dim3(RS, msplit),
-                         dim3(256), 256 * 32 * sizeof(float), stream,
+                         dim3(256), (size_t)SmallKGeo<4>::LDS_BYTES, stream,
                          (const bf16_t*)dy.data_ptr(),
                          (const bf16_t*)x.data_ptr(), dw.data_ptr<float>(),
                          N, H, W, Cp, log2i(Cp), Kp, K, C, (int)ks, msplit,
@@ -1439,7 +1380,7 @@ void bias_grad(const at::Tensor& dy, at::Tensor& db) {
   auto part = at::empty({msplit, (long)Kp},
                         dy.options().dtype(at::kFloat));
   hipLaunchKernelGGL(k_bias_grad, dim3(gx, msplit), dim3(256),
-                     256 * 8 * sizeof(float), stream,
+                     (size_t)BiasGradGeo::LDS_BYTES, stream,
                      (const bf16_t*)dy.data_ptr(), part.data_ptr<float>(),
                      M, Kp, msplit);
   HIP_CHECK_LAST();
