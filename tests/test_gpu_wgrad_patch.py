@@ -12,12 +12,13 @@ on the CPU in fp32/fp64 by an explicit unfold matmul.
 import os
 import subprocess
 import sys
-import zlib
 from pathlib import Path
 
 import numpy as np
 import pytest
 import torch
+
+from wgrad_exact import make_dw0, make_inputs, pow2, reference
 
 pytestmark = pytest.mark.gpu
 
@@ -39,13 +40,6 @@ ACC = [(3, 32, 32, 19, 0), (5, 32, 32, 19, 0), (7, 32, 32, 19, 0),
        (5, 128, 128, 67, 64), (7, 64, 64, 115, 112)]
 
 
-def pow2(c):
-    p = 16
-    while p < c:
-        p *= 2
-    return p
-
-
 def int_id(ks, C, K, W, ch):
     return f"int-k{ks}-c{C}-k{K}-w{W}-ch{ch}"
 
@@ -56,40 +50,6 @@ def acc_id(ks, C, K, W, ch):
 
 def rand_id(ks, C, K, H, W):
     return f"rand-k{ks}-c{C}-k{K}-h{H}-w{W}"
-
-
-def make_inputs(cid, C, K, H, W, integer):
-    """dy (N,H,W,K), x (N,H,W,C) fp32, exactly representable in bf16."""
-    rng = np.random.default_rng(zlib.crc32(cid.encode()))
-    if integer:  # asymmetric by construction: iid integers in [-3, 3]
-        x = rng.integers(-3, 4, size=(N, H, W, C)).astype(np.float32)
-        dy = rng.integers(-3, 4, size=(N, H, W, K)).astype(np.float32)
-    else:
-        x = rng.random((N, H, W, C), dtype=np.float32)
-        dy = rng.standard_normal((N, H, W, K), dtype=np.float32)
-    x = torch.from_numpy(x).bfloat16().float().numpy()
-    dy = torch.from_numpy(dy).bfloat16().float().numpy()
-    return dy, x
-
-
-def make_dw0(cid, ks, C, K):
-    rng = np.random.default_rng(zlib.crc32(cid.encode()) ^ 0x5A5A)
-    return rng.integers(-5, 6, size=(K, C, ks, ks)).astype(np.float32)
-
-
-def reference(dy, x, ks, dtype):
-    """dW[k,c,r,s] = sum_m dY[m,k] * X[m shifted by (r-PAD, s-PAD), c]."""
-    n, H, W, C = x.shape
-    K = dy.shape[3]
-    pad = ks // 2
-    xp = np.zeros((n, H + 2 * pad, W + 2 * pad, C), dtype=dtype)
-    xp[:, pad:pad + H, pad:pad + W] = x
-    dyf = dy.reshape(-1, K).astype(dtype)
-    dw = np.zeros((K, C, ks, ks), dtype=dtype)
-    for r in range(ks):
-        for s in range(ks):
-            dw[:, :, r, s] = dyf.T @ xp[:, r:r + H, s:s + W].reshape(-1, C)
-    return dw
 
 
 # ---------------------------------------------------------------------------

@@ -227,3 +227,67 @@ def test_native_state_plans():
     chans = [spec.K for k, spec in vst.plan if k == "conv"]
     assert chans == [64, 64, 128, 128, 256, 256, 256, 256,
                      512, 512, 512, 512, 512, 512, 512, 512]
+
+
+def test_conv2d_wgrad_plan_protocol(monkeypatch):
+    """conv2d_wgrad_plan is host-only: (kernel, BK, gx, gy, gz) for a shape,
+    launching nothing. The kernel per channel class, the generic grid rule,
+    the per-call knobs and the rejected arguments."""
+    import os
+
+    from waternet_amd.engine.native import WaterNetNativeState
+    from waternet_amd.models.waternet import WaterNet
+    from waternet_amd.ops import ext
+
+    for var in ("WN_WGRAD_PATCH", "WN_WGRAD_M32", "WN_WGRAD_PATCH_CH",
+                "WN_WGRAD_PATCH_BLOCKS", "WN_WGRAD_SMALLK_MSPLIT",
+                "WN_WGRAD_SMALLK_U"):
+        assert var not in os.environ, var
+    plan = ext().conv2d_wgrad_plan
+
+    p = plan(4, 144, 144, 128, 64, 64, 1)
+    assert isinstance(p, tuple) and len(p) == 5 and isinstance(p[0], str)
+    assert all(isinstance(v, int) for v in p[1:])
+    # k_conv_wgrad: BK = min(Kp, 128), gy = ceil(ks^2 Cp / 128), the split
+    # fills 640 blocks and never exceeds the 64-row chunks
+    assert p == ("generic", 64, 1, 1, 640)
+    assert plan(2, 72, 72, 256, 256, 256, 1) == ("generic", 128, 2, 2, 160)
+    assert plan(2, 84, 84, 32, 64, 64, 3) == ("generic", 64, 1, 3, 213)
+    assert plan(1, 3, 5, 64, 64, 64, 1) == ("generic", 64, 1, 1, 1)
+    # BK = 16 has no 32x32 MFMA path
+    assert plan(2, 72, 72, 16, 16, 12, 5) == ("generic16", 16, 1, 4, 160)
+    # the patch classes, from k3 up
+    assert plan(2, 64, 64, 64, 64, 64, 3)[:4] == ("patch", 64, 1, 3)
+    assert plan(2, 64, 64, 128, 64, 64, 5)[:4] == ("patch", 64, 1, 10)
+    assert plan(2, 64, 64, 32, 32, 32, 5)[:4] == ("patch", 32, 1, 5)
+    assert plan(2, 64, 64, 16, 128, 128, 7)[:4] == ("patch16", 64, 2, 7)
+    assert plan(2, 64, 64, 16, 32, 32, 7)[:4] == ("patch16", 32, 1, 7)
+    # K <= 4: one block row per tap, m-slices in y
+    k, bk, gx, gy, gz = plan(2, 64, 64, 64, 16, 3, 3)
+    assert (k, bk, gx, gz) == ("smallk", 4, 9, 1) and gy >= 1
+
+    # every WaterNet layer plans, and the model reaches all but generic16
+    st = WaterNetNativeState(WaterNet())
+    specs = st.cmg_specs + [s for v in st.refiner_specs.values() for s in v]
+    kernels = {plan(16, 112, 112, s.Cp, s.Kp, s.K, s.ks)[0] for s in specs}
+    assert kernels == {"smallk", "patch", "patch16", "generic"}
+
+    # the block-count and chunk-length knobs are read per call
+    base = plan(2, 64, 128, 64, 64, 64, 3)
+    monkeypatch.setenv("WN_WGRAD_PATCH_BLOCKS", "100000")
+    many = plan(2, 64, 128, 64, 64, 64, 3)
+    assert many[:4] == base[:4] and many[4] == 2 * 64 * 2 > base[4]
+    monkeypatch.setenv("WN_WGRAD_PATCH_CH", "112")
+    assert plan(2, 64, 128, 64, 64, 64, 3)[4] == 2 * 64 * 2
+    assert plan(2, 64, 112, 64, 64, 64, 3)[4] == 2 * 64 * 1
+    monkeypatch.delenv("WN_WGRAD_PATCH_BLOCKS")
+    monkeypatch.delenv("WN_WGRAD_PATCH_CH")
+    assert plan(2, 64, 128, 64, 64, 64, 3) == base
+    monkeypatch.setenv("WN_WGRAD_SMALLK_MSPLIT", "5")
+    assert plan(2, 64, 64, 64, 16, 3, 3) == ("smallk", 4, 9, 5, 1)
+    monkeypatch.delenv("WN_WGRAD_SMALLK_MSPLIT")
+
+    for bad in ((2, 8, 8, 64, 64, 64, 2), (2, 8, 8, 48, 64, 64, 3),
+                (2, 8, 8, 64, 64, 65, 3), (0, 8, 8, 64, 64, 64, 3)):
+        with pytest.raises(RuntimeError):
+            plan(*bad)

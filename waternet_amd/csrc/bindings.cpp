@@ -13,6 +13,9 @@ std::tuple<std::string, int64_t, int64_t> conv2d_fwd_plan(
     int64_t N, int64_t H, int64_t W, int64_t Cp, int64_t Kp, int64_t ks);
 void conv2d_wgrad(const at::Tensor& dy, const at::Tensor& x, at::Tensor& dw,
                   int64_t ks);
+std::tuple<std::string, int64_t, int64_t, int64_t, int64_t> conv2d_wgrad_plan(
+    int64_t N, int64_t H, int64_t W, int64_t Cp, int64_t Kp, int64_t K,
+    int64_t ks);
 void bias_grad(const at::Tensor& dy, at::Tensor& db);
 at::Tensor pack_weight_fwd(const at::Tensor& w, int64_t Kp, int64_t Cp);
 at::Tensor pack_weight_dgrad(const at::Tensor& w, int64_t Kp, int64_t Cp);
@@ -81,6 +84,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_fwd_plan", &conv2d_fwd_plan,
         "dispatch decision of conv2d_fwd for a shape: (kernel, BN, gz)");
   m.def("conv2d_wgrad", &conv2d_wgrad,"conv weight grad into NCHW fp32");
+  m.def("conv2d_wgrad_plan", &conv2d_wgrad_plan,
+        "launch decision of conv2d_wgrad for a shape: (kernel, BK, gx, gy, "
+        "gz)");
   m.def("bias_grad", &bias_grad, "bias grad (column sum)");
   m.def("pack_weight_fwd", &pack_weight_fwd);
   m.def("pack_weight_dgrad", &pack_weight_dgrad);

@@ -1185,6 +1185,30 @@ constexpr int WGRAD_PATCH_BLOCKS_MAX = 768;
 constexpr double WGRAD_PATCH16_BLOCKS_K = 80.0;
 constexpr int WGRAD_PATCH16_BLOCKS_MAX = 1024;
 
+constexpr int WG_CH = 64;  // k_conv_wgrad m rows per chunk (glds double-buffer
+                           // budget)
+
+// Which weight-gradient kernel a conv shape runs on, and on what grid. The
+// single source of the dispatch rule: conv2d_wgrad launches what wgrad_plan
+// returns and conv2d_wgrad_plan reports it to the tests.
+enum WgradKernel {
+  WG_SMALLK = 0,
+  WG_PATCH = 1,
+  WG_PATCH16 = 2,
+  WG_GENERIC = 3,    // k_conv_wgrad, 32x32x16 MFMA
+  WG_GENERIC16 = 4   // k_conv_wgrad, 16x16x32 MFMA (BK = 16 or WN_WGRAD_M32=0)
+};
+
+struct WgradPlan {
+  WgradKernel kernel;
+  int BK;          // k tile (small-K: its KMAX = 4 rows)
+  int gx, gy, gz;  // the grid launched; gz is the split-m count (small-K:
+                   // gx taps x gy m-slices, gz = 1)
+  int cls;         // patch kernels: channel class 64 / 32 / 16
+  int ch;          // patch kernels: chunk length 64 / 112
+  int unroll;      // small-K: rows in flight per thread
+};
+
 // Split-m block count of the patch kernels. Their time is main loop +
 // epilogue atomics: T(blocks) ~ a*work/blocks + b*blocks*tile, with work =
 // gx*gy*chunks*k-steps and tile = atomics per block, so the optimum is
@@ -1200,87 +1224,30 @@ inline int patch_split(double work, int tile, int gxgy, double k, int cap,
   return (int)std::min<long>(split, maxChunks);
 }
 
-// Launch of a patch kernel with tile constants G; blocks_k / blocks_max are
-// its patch_split constants. cp is the kernel's Cp argument:
-// k_conv_wgrad_patch takes one, k_conv_wgrad_patch16 (Cp = 16) has none.
-template <class G, class Kern, class... CpArg>
-void launch_wgrad_patch_t(Kern kern, double blocks_k, int blocks_max,
-                          const at::Tensor& dy, const at::Tensor& x,
-                          at::Tensor& dw, const bf16_t* zero16,
-                          hipStream_t stream, CpArg... cp) {
-  const int N = x.size(0), H = x.size(1), W = x.size(2), Cp = x.size(3);
-  const int Kp = dy.size(3);
-  const int K = dw.size(0), C = dw.size(1);
-  const int nSeg = (W + G::CH - 1) / G::CH;
-  const int gx = Kp / G::BK, gy = (Cp / G::CT) * G::KS;
-  const double work = (double)gx * gy * N * H * nSeg * (G::CH / 16);
-  // a block's atomics: its BK x CT tile of one dy row
-  const int split = patch_split(work, G::BK * G::CT * G::KS, gx * gy, blocks_k,
-                                blocks_max, (long)N * H * nSeg);
-  hipLaunchKernelGGL(kern, dim3(gx, gy, split), dim3(256),
-                     (size_t)G::LDS_BYTES, stream,
-                     (const bf16_t*)dy.data_ptr(),
-                     (const bf16_t*)x.data_ptr(), dw.data_ptr<float>(), N, H,
-                     W, cp..., Kp, K, C, nSeg, zero16);
+// WN_WGRAD_PATCH=0, read once per process, forces k_conv_wgrad wherever a
+// patch kernel would run.
+inline bool wgrad_patch_off() {
+  static const bool off = [] {
+    const char* e = getenv("WN_WGRAD_PATCH");
+    return e != nullptr && atoi(e) == 0;
+  }();
+  return off;
+}
+// WN_WGRAD_M32, read once per process: default ON; 0 = the 16x16x32 path.
+inline bool wgrad_m32() {
+  static const bool m32 = [] {
+    const char* e = getenv("WN_WGRAD_M32");
+    return e == nullptr || atoi(e) != 0;
+  }();
+  return m32;
 }
 
-// cls: 64 (Cp and Kp multiples of 64), 32 (32 -> 32) or 16 (Cp = 16).
-void launch_wgrad_patch(const at::Tensor& dy, const at::Tensor& x,
-                        at::Tensor& dw, int ks, int cls,
-                        const bf16_t* zero16, hipStream_t stream) {
-  // chunk length: the instantiated CH that pads a row the least (112 = 7
-  // k-steps covers the flagship's 112-pixel rows exactly; 64 divides the
-  // 256/512 widths). WN_WGRAD_PATCH_CH overrides it for tests and A/B
-  // runs; it is read per call so one process can exercise both.
-  const char* fe = getenv("WN_WGRAD_PATCH_CH");
-  const int force_ch = fe ? atoi(fe) : 0;
-  const int W = x.size(2);
-  int ch = 64;
-  if (cls == 64 || cls == 16) {
-    const int pad64 = (W + 63) / 64 * 64, pad112 = (W + 111) / 112 * 112;
-    ch = (pad112 < pad64) ? 112 : 64;
-    if (force_ch == 64 || force_ch == 112) ch = force_ch;
-  }
-  const int bk16 = dy.size(3) == 32 ? 32 : 64;  // cls 16: Kp = 32 or n*64
-  const int Cp = x.size(3);
-  dispatch_int<3, 5, 7>(ks, "kernel size", [&](auto ks_const) {
-    constexpr int KSV = decltype(ks_const)::value;
-    dispatch_int<64, 112>(ch, "patch chunk length", [&](auto ch_const) {
-      constexpr int CHV = decltype(ch_const)::value;
-      if (cls == 16)
-        dispatch_int<32, 64>(bk16, "patch16 k tile", [&](auto bk_const) {
-          constexpr int BKV = decltype(bk_const)::value;
-          launch_wgrad_patch_t<Patch16Geo<KSV, BKV, CHV>>(
-              k_conv_wgrad_patch16<KSV, BKV, CHV>, WGRAD_PATCH16_BLOCKS_K,
-              WGRAD_PATCH16_BLOCKS_MAX, dy, x, dw, zero16, stream);
-        });
-      else if (cls == 32)
-        launch_wgrad_patch_t<PatchGeo<KSV, 32, 32, 64>>(
-            k_conv_wgrad_patch<KSV, 32, 32, 64>, WGRAD_PATCH_BLOCKS_K,
-            WGRAD_PATCH_BLOCKS_MAX, dy, x, dw, zero16, stream, Cp);
-      else
-        launch_wgrad_patch_t<PatchGeo<KSV, 64, 64, CHV>>(
-            k_conv_wgrad_patch<KSV, 64, 64, CHV>, WGRAD_PATCH_BLOCKS_K,
-            WGRAD_PATCH_BLOCKS_MAX, dy, x, dw, zero16, stream, Cp);
-    });
-  });
-}
-
-}  // namespace
-
-void conv2d_wgrad(const at::Tensor& dy, const at::Tensor& x, at::Tensor& dw,
-                  int64_t ks) {
-  TORCH_CHECK(dy.is_cuda() && dy.dtype() == at::kBFloat16);
-  TORCH_CHECK(x.is_cuda() && x.dtype() == at::kBFloat16);
-  TORCH_CHECK(dw.is_cuda() && dw.dtype() == at::kFloat && dw.dim() == 4);
-  TORCH_CHECK(dy.is_contiguous() && x.is_contiguous() && dw.is_contiguous());
-  const int N = x.size(0), H = x.size(1), W = x.size(2), Cp = x.size(3);
-  const int Kp = dy.size(3);
-  const int K = dw.size(0), C = dw.size(1);
-  TORCH_CHECK(dw.size(2) == ks && dw.size(3) == ks);
-  hipStream_t stream = at::cuda::getCurrentHIPStream();
+inline WgradPlan wgrad_plan(int N, int H, int W, int Cp, int Kp, int K,
+                            int ks) {
+  WgradPlan p{};
+  const long M = (long)N * H * W;
   if (K <= 4) {  // output convs (K=3): VALU outer-product path
-    const int RS = (int)(ks * ks);
+    const int RS = ks * ks;
     // m-slices per tap. A block pays a fixed LDS tree reduce + atomics, so
     // T(blocks) ~ a*work/blocks + b*blocks as for the patch kernel: blocks ~
     // sqrt(work) with work = taps * rows * channel octets, up to one resident
@@ -1293,69 +1260,193 @@ void conv2d_wgrad(const at::Tensor& dy, const at::Tensor& x, at::Tensor& dw,
     int msplit = std::max(1, blocks / RS);
     if (const char* me = getenv("WN_WGRAD_SMALLK_MSPLIT"))
       msplit = std::max(1, atoi(me));
-    int unroll = WGRAD_SMALLK_U;
-    if (const char* ue = getenv("WN_WGRAD_SMALLK_U")) unroll = atoi(ue);
+    p.unroll = WGRAD_SMALLK_U;
+    if (const char* ue = getenv("WN_WGRAD_SMALLK_U")) p.unroll = atoi(ue);
     const int MR = 256 / (Cp / 8);
-    msplit = (int)std::min<long>(msplit, ((long)N * H * W + MR - 1) / MR);
-    dispatch_int<1, 2, 4, 6>(unroll, "WN_WGRAD_SMALLK_U", [&](auto u_const) {
+    msplit = (int)std::min<long>(msplit, (M + MR - 1) / MR);
+    p.kernel = WG_SMALLK;
+    p.BK = 4;
+    p.gx = RS;
+    p.gy = msplit;
+    p.gz = 1;
+    return p;
+  }
+  // Patch kernel (one X row segment staged once for all KS dx taps) for
+  // every channel class it is instantiated for: each measured faster than
+  // k_conv_wgrad on MI355X, the Cp = 16 tap-pair classes included (table:
+  // docs/KERNELS.md, wgrad section). cls: 64 (Cp and Kp multiples of 64),
+  // 32 (32 -> 32) or 16 (Cp = 16).
+  const int cls = (Cp % 64 == 0 && Kp % 64 == 0)             ? 64
+                  : (Cp == 32 && Kp == 32)                   ? 32
+                  : (Cp == 16 && (Kp == 32 || Kp % 64 == 0)) ? 16
+                                                             : 0;
+  if (!wgrad_patch_off() && ks >= 3 && cls != 0) {
+    // chunk length: the instantiated CH that pads a row the least (112 = 7
+    // k-steps covers the flagship's 112-pixel rows exactly; 64 divides the
+    // 256/512 widths). WN_WGRAD_PATCH_CH overrides it for tests and A/B
+    // runs; it is read per call so one process can exercise both.
+    const char* fe = getenv("WN_WGRAD_PATCH_CH");
+    const int force_ch = fe ? atoi(fe) : 0;
+    int ch = 64;
+    if (cls == 64 || cls == 16) {
+      const int pad64 = (W + 63) / 64 * 64, pad112 = (W + 111) / 112 * 112;
+      ch = (pad112 < pad64) ? 112 : 64;
+      if (force_ch == 64 || force_ch == 112) ch = force_ch;
+    }
+    // tile: BK x CT of one dy row; cls 16: Kp = 32 or n*64
+    const int BK = cls == 64 ? 64 : cls == 32 ? 32 : (Kp == 32 ? 32 : 64);
+    const int CT = cls;
+    const int nSeg = (W + ch - 1) / ch;
+    p.kernel = cls == 16 ? WG_PATCH16 : WG_PATCH;
+    p.BK = BK;
+    p.cls = cls;
+    p.ch = ch;
+    p.gx = Kp / BK;
+    p.gy = (Cp / CT) * ks;
+    const double work = (double)p.gx * p.gy * N * H * nSeg * (ch / 16);
+    // a block's atomics: its BK x CT tile of one dy row
+    p.gz = cls == 16
+               ? patch_split(work, BK * CT * ks, p.gx * p.gy,
+                             WGRAD_PATCH16_BLOCKS_K, WGRAD_PATCH16_BLOCKS_MAX,
+                             (long)N * H * nSeg)
+               : patch_split(work, BK * CT * ks, p.gx * p.gy,
+                             WGRAD_PATCH_BLOCKS_K, WGRAD_PATCH_BLOCKS_MAX,
+                             (long)N * H * nSeg);
+    return p;
+  }
+  const int KG = ks * ks * Cp;
+  p.BK = std::min(Kp, 128);
+  p.gx = (Kp + p.BK - 1) / p.BK;
+  p.gy = (KG + 127) / 128;
+  // split so gx*gy*split fills 256 CUs x ~3 resident blocks
+  const int split = std::max(1, 640 / std::max(1, p.gx * p.gy));
+  const long nChunks = (M + WG_CH - 1) / WG_CH;
+  p.gz = (int)std::min<long>(split, nChunks);
+  // the 32x32 MFMA path exists for BK >= 32
+  p.kernel = (p.BK >= 32 && wgrad_m32()) ? WG_GENERIC : WG_GENERIC16;
+  return p;
+}
+
+// Launch of a patch kernel with tile constants G on the plan's grid. cp is
+// the kernel's Cp argument: k_conv_wgrad_patch takes one,
+// k_conv_wgrad_patch16 (Cp = 16) has none.
+template <class G, class Kern, class... CpArg>
+void launch_wgrad_patch_t(Kern kern, const WgradPlan& plan,
+                          const at::Tensor& dy, const at::Tensor& x,
+                          at::Tensor& dw, const bf16_t* zero16,
+                          hipStream_t stream, CpArg... cp) {
+  const int N = x.size(0), H = x.size(1), W = x.size(2);
+  const int Kp = dy.size(3);
+  const int K = dw.size(0), C = dw.size(1);
+  TORCH_INTERNAL_ASSERT(G::BK == plan.BK && G::CT == plan.cls &&
+                        (G::CH == plan.ch || plan.cls == 32));
+  const int nSeg = (W + G::CH - 1) / G::CH;
+  hipLaunchKernelGGL(kern, dim3(plan.gx, plan.gy, plan.gz), dim3(256),
+                     (size_t)G::LDS_BYTES, stream,
+                     (const bf16_t*)dy.data_ptr(),
+                     (const bf16_t*)x.data_ptr(), dw.data_ptr<float>(), N, H,
+                     W, cp..., Kp, K, C, nSeg, zero16);
+}
+
+void launch_wgrad_patch(const at::Tensor& dy, const at::Tensor& x,
+                        at::Tensor& dw, int ks, const WgradPlan& plan,
+                        const bf16_t* zero16, hipStream_t stream) {
+  const int Cp = x.size(3);
+  dispatch_int<3, 5, 7>(ks, "kernel size", [&](auto ks_const) {
+    constexpr int KSV = decltype(ks_const)::value;
+    dispatch_int<64, 112>(plan.ch, "patch chunk length", [&](auto ch_const) {
+      constexpr int CHV = decltype(ch_const)::value;
+      if (plan.cls == 16)
+        dispatch_int<32, 64>(plan.BK, "patch16 k tile", [&](auto bk_const) {
+          constexpr int BKV = decltype(bk_const)::value;
+          launch_wgrad_patch_t<Patch16Geo<KSV, BKV, CHV>>(
+              k_conv_wgrad_patch16<KSV, BKV, CHV>, plan, dy, x, dw, zero16,
+              stream);
+        });
+      else if (plan.cls == 32)
+        launch_wgrad_patch_t<PatchGeo<KSV, 32, 32, 64>>(
+            k_conv_wgrad_patch<KSV, 32, 32, 64>, plan, dy, x, dw, zero16,
+            stream, Cp);
+      else
+        launch_wgrad_patch_t<PatchGeo<KSV, 64, 64, CHV>>(
+            k_conv_wgrad_patch<KSV, 64, 64, CHV>, plan, dy, x, dw, zero16,
+            stream, Cp);
+    });
+  });
+}
+
+}  // namespace
+
+// The launch decision conv2d_wgrad would take for an (N,H,W,Cp) input, a
+// (N,H,W,Kp) output gradient and K logical output channels: (kernel, BK, gx,
+// gy, gz). Host only: launches nothing and touches no device memory. Reads
+// the same environment variables as conv2d_wgrad, at the same times.
+std::tuple<std::string, int64_t, int64_t, int64_t, int64_t> conv2d_wgrad_plan(
+    int64_t N, int64_t H, int64_t W, int64_t Cp, int64_t Kp, int64_t K,
+    int64_t ks) {
+  TORCH_CHECK(ks == 1 || ks == 3 || ks == 5 || ks == 7,
+              "unsupported kernel size ", ks);
+  TORCH_CHECK(N >= 1 && H >= 1 && W >= 1 && K >= 1 && Cp >= 16 && Kp >= 16 &&
+                  (Cp & (Cp - 1)) == 0 && (Kp & (Kp - 1)) == 0 && K <= Kp,
+              "conv2d_wgrad_plan: Cp and Kp powers of two >= 16, K <= Kp");
+  const WgradPlan p = wgrad_plan((int)N, (int)H, (int)W, (int)Cp, (int)Kp,
+                                 (int)K, (int)ks);
+  const char* name = p.kernel == WG_SMALLK      ? "smallk"
+                     : p.kernel == WG_PATCH     ? "patch"
+                     : p.kernel == WG_PATCH16   ? "patch16"
+                     : p.kernel == WG_GENERIC   ? "generic"
+                                                : "generic16";
+  return {name, p.BK, p.gx, p.gy, p.gz};
+}
+
+void conv2d_wgrad(const at::Tensor& dy, const at::Tensor& x, at::Tensor& dw,
+                  int64_t ks) {
+  TORCH_CHECK(dy.is_cuda() && dy.dtype() == at::kBFloat16);
+  TORCH_CHECK(x.is_cuda() && x.dtype() == at::kBFloat16);
+  TORCH_CHECK(dw.is_cuda() && dw.dtype() == at::kFloat && dw.dim() == 4);
+  TORCH_CHECK(dy.is_contiguous() && x.is_contiguous() && dw.is_contiguous());
+  const int N = x.size(0), H = x.size(1), W = x.size(2), Cp = x.size(3);
+  const int Kp = dy.size(3);
+  const int K = dw.size(0), C = dw.size(1);
+  TORCH_CHECK(dw.size(2) == ks && dw.size(3) == ks);
+  hipStream_t stream = at::cuda::getCurrentHIPStream();
+  const WgradPlan plan = wgrad_plan(N, H, W, Cp, Kp, K, (int)ks);
+  if (plan.kernel == WG_SMALLK) {
+    dispatch_int<1, 2, 4, 6>(plan.unroll, "WN_WGRAD_SMALLK_U",
+                             [&](auto u_const) {
       constexpr int UV = decltype(u_const)::value;
-      hipLaunchKernelGGL((k_wgrad_smallk<4, UV>), dim3(RS, msplit),
+      hipLaunchKernelGGL((k_wgrad_smallk<4, UV>), dim3(plan.gx, plan.gy),
                          dim3(256), (size_t)SmallKGeo<4>::LDS_BYTES, stream,
                          (const bf16_t*)dy.data_ptr(),
                          (const bf16_t*)x.data_ptr(), dw.data_ptr<float>(),
-                         N, H, W, Cp, log2i(Cp), Kp, K, C, (int)ks, msplit,
+                         N, H, W, Cp, log2i(Cp), Kp, K, C, (int)ks, plan.gy,
                          MagicDiv::make((unsigned)(H * W)).mul,
                          MagicDiv::make((unsigned)W).mul);
     });
     HIP_CHECK_LAST();
     return;
   }
-  // Patch kernel (one X row segment staged once for all KS dx taps) for
-  // every channel class it is instantiated for: each measured faster than
-  // k_conv_wgrad on MI355X, the Cp = 16 tap-pair classes included (table:
-  // docs/KERNELS.md, wgrad section). WN_WGRAD_PATCH=0 forces k_conv_wgrad
-  // everywhere.
-  static const bool patch_off = [] {
-    const char* e = getenv("WN_WGRAD_PATCH");
-    return e != nullptr && atoi(e) == 0;
-  }();
-  const int cls = (Cp % 64 == 0 && Kp % 64 == 0)             ? 64
-                  : (Cp == 32 && Kp == 32)                   ? 32
-                  : (Cp == 16 && (Kp == 32 || Kp % 64 == 0)) ? 16
-                                                             : 0;
-  if (!patch_off && ks >= 3 && cls != 0) {
-    launch_wgrad_patch(dy, x, dw, (int)ks, cls, zero16_for(x), stream);
+  if (plan.kernel == WG_PATCH || plan.kernel == WG_PATCH16) {
+    launch_wgrad_patch(dy, x, dw, (int)ks, plan, zero16_for(x), stream);
     HIP_CHECK_LAST();
     return;
   }
-  const int KG = (int)(ks * ks) * Cp;
-  const int BK = std::min(Kp, 128);
-  constexpr int WG_CH = 64;  // m rows per chunk (glds double-buffer budget)
-  const int gx = (Kp + BK - 1) / BK, gy = (KG + 127) / 128;
-  // split so gx*gy*split fills 256 CUs x ~3 resident blocks
-  int split = std::max(1, 640 / std::max(1, gx * gy));
-  const long nChunks = ((long)N * H * W + WG_CH - 1) / WG_CH;
-  split = (int)std::min<long>(split, nChunks);
   const bf16_t* zptr = zero16_for(x);
-  static const bool use_m32 = [] {
-    const char* e = getenv("WN_WGRAD_M32");
-    return e == nullptr || atoi(e) != 0;  // default ON; 0 = 16x16 path
-  }();
   dispatch_int<1, 3, 5, 7>((int)ks, "kernel size", [&](auto ks_const) {
     // BK = min(Kp, 128) with Kp a power of two >= 16
-    dispatch_int_or<16, 128, 64, 32, 16>(BK, [&](auto bk_const) {
+    dispatch_int_or<16, 128, 64, 32, 16>(plan.BK, [&](auto bk_const) {
       constexpr int KSV = decltype(ks_const)::value;
       constexpr int BKV = decltype(bk_const)::value;
-      // the 32x32 MFMA path exists for BK >= 32
-      dispatch_int<0, 1>(BKV >= 32 && use_m32, "M32", [&](auto m32_const) {
+      dispatch_int<0, 1>(plan.kernel == WG_GENERIC, "M32",
+                         [&](auto m32_const) {
         constexpr bool M32V = BKV >= 32 && decltype(m32_const)::value != 0;
         using G = WgradGeo<BKV, WG_CH>;
         hipLaunchKernelGGL((k_conv_wgrad<KSV, BKV, WG_CH, M32V>),
-                           dim3(gx, gy, split), dim3(256),
+                           dim3(plan.gx, plan.gy, plan.gz), dim3(256),
                            (size_t)G::LDS_BYTES, stream,
                            (const bf16_t*)dy.data_ptr(),
                            (const bf16_t*)x.data_ptr(), dw.data_ptr<float>(),
-                           N, H, W, Cp, log2i(Cp), Kp, K, C, split,
+                           N, H, W, Cp, log2i(Cp), Kp, K, C, plan.gz,
                            MagicDiv::make((unsigned)(H * W)).mul,
                            MagicDiv::make((unsigned)W).mul, zptr);
       });
@@ -1365,11 +1456,19 @@ void conv2d_wgrad(const at::Tensor& dy, const at::Tensor& x, at::Tensor& dw,
 }
 
 void bias_grad(const at::Tensor& dy, at::Tensor& db) {
-  TORCH_CHECK(dy.is_cuda() && dy.dtype() == at::kBFloat16);
-  TORCH_CHECK(db.is_cuda() && db.dtype() == at::kFloat);
+  TORCH_CHECK(dy.is_cuda() && dy.dtype() == at::kBFloat16 && dy.dim() == 4 &&
+                  dy.is_contiguous(),
+              "bias_grad: dy must be contiguous (N,H,W,Kp) bf16 on the GPU");
+  TORCH_CHECK(db.is_cuda() && db.dtype() == at::kFloat && db.dim() == 1 &&
+                  db.is_contiguous() && db.device() == dy.device(),
+              "bias_grad: db must be a contiguous 1-D fp32 tensor on dy's "
+              "device");
   const int Kp = dy.size(3);
+  TORCH_CHECK(Kp >= 8 && Kp % 8 == 0, "bias_grad: Kp must be a multiple of 8");
   const long M = dy.numel() / Kp;
   const int K = db.size(0);
+  TORCH_CHECK(K <= Kp, "bias_grad: db longer than Kp");
+  if (M == 0 || K == 0) return;
   const int ngrp = Kp / 8;
   const int KGR = std::min(ngrp, 32);
   const int gx = (ngrp + KGR - 1) / KGR;

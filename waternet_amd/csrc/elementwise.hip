@@ -16,6 +16,11 @@ constexpr int TPB = 256;
 inline int grid1d(long n, int tpb = TPB, int cap = 4096) {
   return (int)std::min<long>(cap, (n + tpb - 1) / tpb);
 }
+// The kernels below index raw data_ptr()s as dense arrays: a tensor they are
+// handed is a contiguous bf16 tensor on the GPU.
+inline bool dense_bf16(const at::Tensor& t) {
+  return t.is_cuda() && t.dtype() == at::kBFloat16 && t.is_contiguous();
+}
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -611,14 +616,25 @@ at::Tensor u8_to_nhwc(const at::Tensor& x, int64_t Cp) {
 
 at::Tensor act_bwd_bias(const at::Tensor& dy, const at::Tensor& y,
                         int64_t act, at::Tensor& db) {
-  TORCH_CHECK(dy.is_cuda() && dy.dtype() == at::kBFloat16 && dy.dim() == 4);
-  TORCH_CHECK(db.is_cuda() && db.dtype() == at::kFloat);
+  TORCH_CHECK(dense_bf16(dy) && dense_bf16(y) && dy.dim() == 4,
+              "act_bwd_bias: dy and y must be contiguous (N,H,W,Kp) bf16 on "
+              "the GPU");
+  TORCH_CHECK(y.sizes() == dy.sizes() && y.device() == dy.device(),
+              "act_bwd_bias: dy and y differ in shape or device");
+  TORCH_CHECK(db.is_cuda() && db.dtype() == at::kFloat && db.dim() == 1 &&
+                  db.is_contiguous() && db.device() == dy.device(),
+              "act_bwd_bias: db must be a contiguous 1-D fp32 tensor on dy's "
+              "device");
+  TORCH_CHECK(act == ACT_RELU || act == ACT_SIGMOID,
+              "act_bwd_bias: act must be relu (1) or sigmoid (2)");
   const int Kp = (int)dy.size(3);
-  TORCH_CHECK(Kp <= 128 && (Kp & (Kp - 1)) == 0, "Kp power of two <= 128");
+  TORCH_CHECK(Kp >= 8 && Kp <= 128 && (Kp & (Kp - 1)) == 0,
+              "act_bwd_bias: Kp power of two in [8, 128]");
   const int K = (int)db.size(0);
+  TORCH_CHECK(K <= Kp, "act_bwd_bias: db longer than Kp");
   auto dpre = at::empty_like(dy);
   const long n = dy.numel();
-  TORCH_CHECK(n % 8 == 0);
+  if (n == 0 || K == 0) return dpre;
   const long n8 = n / 8;
   // blocks*blockDim*8 must be divisible by Kp: 256*8 = 2048 is divisible
   // by every Kp <= 128, so any block count works
@@ -691,9 +707,21 @@ at::Tensor nhwc_to_nchw(const at::Tensor& x, int64_t C) {
 
 at::Tensor fusion_fwd(const at::Tensor& maps, const at::Tensor& rwb,
                       const at::Tensor& rce, const at::Tensor& rgc) {
+  TORCH_CHECK(dense_bf16(maps) && dense_bf16(rwb) && dense_bf16(rce) &&
+                  dense_bf16(rgc),
+              "fusion_fwd: all tensors must be contiguous bf16 on the GPU");
+  TORCH_CHECK(maps.dim() == 4 && maps.size(3) == 16,
+              "fusion_fwd: maps must be (N,H,W,16)");
+  TORCH_CHECK(rwb.sizes() == maps.sizes() && rce.sizes() == maps.sizes() &&
+                  rgc.sizes() == maps.sizes() &&
+                  rwb.device() == maps.device() &&
+                  rce.device() == maps.device() &&
+                  rgc.device() == maps.device(),
+              "fusion_fwd: tensors differ in shape or device");
   const long N = maps.size(0), H = maps.size(1), W = maps.size(2);
   const long NHW = N * H * W;
   auto out = at::empty_like(maps);
+  if (NHW == 0) return out;
   hipLaunchKernelGGL(k_fusion_fwd, dim3(grid1d(NHW)), dim3(TPB), 0,
                      cur_stream(), (const bf16_t*)maps.data_ptr(),
                      (const bf16_t*)rwb.data_ptr(),
@@ -709,12 +737,26 @@ std::vector<at::Tensor> fusion_bwd(const at::Tensor& dout,
                                    const at::Tensor& rwb,
                                    const at::Tensor& rce,
                                    const at::Tensor& rgc) {
+  TORCH_CHECK(dense_bf16(dout) && dense_bf16(maps) && dense_bf16(rwb) &&
+                  dense_bf16(rce) && dense_bf16(rgc),
+              "fusion_bwd: all tensors must be contiguous bf16 on the GPU");
+  TORCH_CHECK(maps.dim() == 4 && maps.size(3) == 16,
+              "fusion_bwd: maps must be (N,H,W,16)");
+  TORCH_CHECK(dout.sizes() == maps.sizes() && rwb.sizes() == maps.sizes() &&
+                  rce.sizes() == maps.sizes() &&
+                  rgc.sizes() == maps.sizes() &&
+                  dout.device() == maps.device() &&
+                  rwb.device() == maps.device() &&
+                  rce.device() == maps.device() &&
+                  rgc.device() == maps.device(),
+              "fusion_bwd: tensors differ in shape or device");
   const long N = maps.size(0), H = maps.size(1), W = maps.size(2);
   const long NHW = N * H * W;
   auto dmaps = at::empty_like(maps);
   auto drwb = at::empty_like(maps);
   auto drce = at::empty_like(maps);
   auto drgc = at::empty_like(maps);
+  if (NHW == 0) return {dmaps, drwb, drce, drgc};
   hipLaunchKernelGGL(k_fusion_bwd, dim3(grid1d(NHW)), dim3(TPB), 0,
                      cur_stream(), (const bf16_t*)dout.data_ptr(),
                      (const bf16_t*)maps.data_ptr(),
@@ -728,8 +770,15 @@ std::vector<at::Tensor> fusion_bwd(const at::Tensor& dout,
 }
 
 at::Tensor act_bwd(const at::Tensor& dy, const at::Tensor& y, int64_t act) {
+  TORCH_CHECK(dense_bf16(dy) && dense_bf16(y),
+              "act_bwd: dy and y must be contiguous bf16 on the GPU");
+  TORCH_CHECK(y.sizes() == dy.sizes() && y.device() == dy.device(),
+              "act_bwd: dy and y differ in shape or device");
+  TORCH_CHECK(act == ACT_RELU || act == ACT_SIGMOID,
+              "act_bwd: act must be relu (1) or sigmoid (2)");
   auto dpre = at::empty_like(dy);
   const long n = dy.numel();
+  if (n == 0) return dpre;
   hipLaunchKernelGGL(k_act_bwd, dim3(grid1d((n + 7) / 8)), dim3(TPB), 0,
                      cur_stream(),
                      (const bf16_t*)dy.data_ptr(),
@@ -790,8 +839,16 @@ at::Tensor sqdiff255_sum(const at::Tensor& a, const at::Tensor& b,
 
 at::Tensor sqdiff255_bwd(const at::Tensor& a, const at::Tensor& b,
                          const at::Tensor& gscale, double sign) {
+  TORCH_CHECK(dense_bf16(a) && dense_bf16(b),
+              "sqdiff255_bwd: a and b must be contiguous bf16 on the GPU");
+  TORCH_CHECK(b.sizes() == a.sizes() && b.device() == a.device(),
+              "sqdiff255_bwd: a and b differ in shape or device");
+  TORCH_CHECK(gscale.is_cuda() && gscale.dtype() == at::kFloat &&
+                  gscale.numel() == 1 && gscale.device() == a.device(),
+              "sqdiff255_bwd: gscale must be one fp32 value on a's device");
   auto da = at::empty_like(a);
   const long n = a.numel();
+  if (n == 0) return da;
   hipLaunchKernelGGL(k_sqdiff255_bwd, dim3(grid1d(n)), dim3(TPB), 0,
                      cur_stream(), (const bf16_t*)a.data_ptr(),
                      (const bf16_t*)b.data_ptr(), gscale.data_ptr<float>(),

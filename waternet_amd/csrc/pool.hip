@@ -58,12 +58,16 @@ __global__ void k_maxpool_bwd(const bf16_t* __restrict__ dy,
 }
 
 std::vector<at::Tensor> maxpool2x2_fwd(const at::Tensor& x) {
-  TORCH_CHECK(x.is_cuda() && x.dtype() == at::kBFloat16 && x.dim() == 4);
+  TORCH_CHECK(x.is_cuda() && x.dtype() == at::kBFloat16 && x.dim() == 4 &&
+                  x.is_contiguous(),
+              "maxpool2x2_fwd: x must be contiguous (N,H,W,Cp) bf16 on the "
+              "GPU");
   const long N = x.size(0), H = x.size(1), W = x.size(2), Cp = x.size(3);
   const long OH = H / 2, OW = W / 2;
   auto y = at::empty({N, OH, OW, Cp}, x.options());
   auto idx = at::empty({N, OH, OW, Cp}, x.options().dtype(at::kByte));
   const long NOHW = N * OH * OW;
+  if (NOHW * Cp == 0) return {y, idx};
   const int blocks = (int)std::min<long>(4096, (NOHW * Cp + 255) / 256);
   hipLaunchKernelGGL(k_maxpool_fwd, dim3(blocks), dim3(256), 0, cur_stream(),
                      (const bf16_t*)x.data_ptr(), (bf16_t*)y.data_ptr(),
@@ -75,10 +79,22 @@ std::vector<at::Tensor> maxpool2x2_fwd(const at::Tensor& x) {
 
 at::Tensor maxpool2x2_bwd(const at::Tensor& dy, const at::Tensor& idx,
                           int64_t H, int64_t W) {
+  TORCH_CHECK(dy.is_cuda() && dy.dtype() == at::kBFloat16 && dy.dim() == 4 &&
+                  dy.is_contiguous(),
+              "maxpool2x2_bwd: dy must be contiguous (N,OH,OW,Cp) bf16 on "
+              "the GPU");
+  TORCH_CHECK(idx.is_cuda() && idx.dtype() == at::kByte &&
+                  idx.is_contiguous() && idx.sizes() == dy.sizes() &&
+                  idx.device() == dy.device(),
+              "maxpool2x2_bwd: idx must be contiguous uint8 of dy's shape on "
+              "dy's device");
   const long N = dy.size(0), OH = dy.size(1), OW = dy.size(2),
              Cp = dy.size(3);
+  TORCH_CHECK(H / 2 == OH && W / 2 == OW,
+              "maxpool2x2_bwd: (H, W) does not pool to dy's (OH, OW)");
   auto dx = at::zeros({N, H, W, Cp}, dy.options());
   const long NOHW = N * OH * OW;
+  if (NOHW * Cp == 0) return dx;
   const int blocks = (int)std::min<long>(4096, (NOHW * Cp + 255) / 256);
   hipLaunchKernelGGL(k_maxpool_bwd, dim3(blocks), dim3(256), 0, cur_stream(),
                      (const bf16_t*)dy.data_ptr(), idx.data_ptr<uint8_t>(),
