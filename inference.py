@@ -39,6 +39,10 @@ def parse_args(argv=None):
                         help="output subdirectory name under ./output")
     parser.add_argument("--show-split", action="store_true",
                         help="write before/after composites")
+    parser.add_argument("--report-quality", action="store_true",
+                        help="print no-reference UIQM/UCIQE before and "
+                             "after per source and append them to "
+                             "<savedir>/quality.csv")
     return parser.parse_args(argv)
 
 
@@ -103,12 +107,59 @@ def _gpu_engine(model, h, w, device):
     return eng
 
 
+QUALITY_HEADER = ("source,frames,uiqm_before,uiqm_after,uciqe_before,"
+                  "uciqe_after,uicm_before,uicm_after,uism_before,uism_after,"
+                  "uiconm_before,uiconm_after")
+
+
+class QualityReport:
+    """--report-quality state of one source: the (2,5) before/after
+    no-reference metrics summed over its frames. On the GPU path the sum
+    stays on the device and is read once, in finish()."""
+
+    def __init__(self):
+        self.total = None
+        self.frames = 0
+
+    def add(self, pair):
+        self.total = pair if self.total is None else self.total + pair
+        self.frames += 1
+
+    def add_cpu(self, before: np.ndarray, after: np.ndarray):
+        from waternet_amd.utils.nr_metrics import nr_metrics
+
+        self.add(np.concatenate([nr_metrics(before), nr_metrics(after)]))
+
+    def finish(self, name: str, savedir: Path):
+        if self.frames == 0:
+            return
+        total = self.total
+        if isinstance(total, torch.Tensor):
+            total = total.cpu().numpy()  # the one host read of this source
+        m = total / self.frames
+        # m rows: before, after; columns: uicm, uism, uiconm, uiqm, uciqe
+        print(f"{name}: UIQM {m[0, 3]:.4f} -> {m[1, 3]:.4f}, "
+              f"UCIQE {m[0, 4]:.4f} -> {m[1, 4]:.4f} "
+              f"({self.frames} frame{'s' if self.frames != 1 else ''})")
+        savedir.mkdir(parents=True, exist_ok=True)
+        csv = savedir / "quality.csv"
+        new = not csv.exists()
+        with open(csv, "a") as f:
+            if new:
+                f.write(QUALITY_HEADER + "\n")
+            vals = [m[r, c] for c in (3, 4, 0, 1, 2) for r in (0, 1)]
+            f.write(",".join([name, str(self.frames)]
+                             + ["%.6f" % v for v in vals]) + "\n")
+
+
 @torch.no_grad()
-def enhance_frame(model, rgb: np.ndarray, device) -> np.ndarray:
+def enhance_frame(model, rgb: np.ndarray, device,
+                  quality=None) -> np.ndarray:
     """uint8 HWC RGB -> enhanced uint8 HWC RGB. On GPU the whole frame
     pipeline (preprocess + forward + postprocess) runs as a hipGraph-
     captured on-device pipeline; on CPU the reference-semantics numpy
-    transforms + eager model run."""
+    transforms + eager model run. A QualityReport, when given, is fed the
+    frame's before/after no-reference metrics."""
     if device.type == "cuda":
         from waternet_amd.ops import native_available
 
@@ -118,15 +169,20 @@ def enhance_frame(model, rgb: np.ndarray, device) -> np.ndarray:
             padded, h, w = pad8(rgb)
             eng = _gpu_engine(model, padded.shape[0], padded.shape[1],
                               device)
-            return eng.infer_frame(padded)[:h, :w]
+            out = eng.infer_frame(padded)[:h, :w]
+            if quality is not None:
+                quality.add(eng.frame_quality(h, w))
+            return out
     wb, gc, he = transform(rgb)
     rgb_ten = arr2ten(rgb, add_batch_dim=True).to(device)
     wb_ten = arr2ten(wb, add_batch_dim=True).to(device)
     gc_ten = arr2ten(gc, add_batch_dim=True).to(device)
     he_ten = arr2ten(he, add_batch_dim=True).to(device)
     # he fills the `ce` slot — reference call order (inference.py:191)
-    out = model(rgb_ten, wb_ten, he_ten, gc_ten)
-    return ten2arr(out)[0]
+    out = ten2arr(model(rgb_ten, wb_ten, he_ten, gc_ten))[0]
+    if quality is not None:
+        quality.add_cpu(rgb, out)
+    return out
 
 
 def compose_split(before: np.ndarray, after: np.ndarray) -> np.ndarray:
@@ -145,33 +201,41 @@ def compose_split(before: np.ndarray, after: np.ndarray) -> np.ndarray:
     return np.asarray(im)
 
 
-def run_image(model, path: Path, savedir: Path, device, show_split):
+def run_image(model, path: Path, savedir: Path, device, show_split,
+              report_quality=False):
     from PIL import Image
 
+    quality = QualityReport() if report_quality else None
     with Image.open(path) as im:
         rgb = np.asarray(im.convert("RGB"))
-    out = enhance_frame(model, rgb, device)
+    out = enhance_frame(model, rgb, device, quality)
     result = compose_split(rgb, out) if show_split else out
     savedir.mkdir(parents=True, exist_ok=True)  # late, ref inference.py:198
     Image.fromarray(result).save(savedir / path.name)
+    if quality is not None:
+        quality.finish(path.name, savedir)
 
 
-def run_video(model, path: Path, savedir: Path, device, show_split):
+def run_video(model, path: Path, savedir: Path, device, show_split,
+              report_quality=False):
     from waternet_amd.engine.video import FFmpegReader, FFmpegWriter
 
+    quality = QualityReport() if report_quality else None
     reader = FFmpegReader(path)
     savedir.mkdir(parents=True, exist_ok=True)  # late, ref inference.py:198
     outpath = savedir / path.name
     writer = FFmpegWriter(outpath, reader.width, reader.height, reader.fps)
     n = 0
     for frame in reader:
-        out = enhance_frame(model, frame, device)
+        out = enhance_frame(model, frame, device, quality)
         writer.write(compose_split(frame, out) if show_split else out)
         n += 1
         if n % 50 == 0:
             print(f"{n} frames processed")
     writer.close()
     print(f"Wrote {n} frames to {outpath}")
+    if quality is not None:
+        quality.finish(path.name, savedir)
 
 
 def main(argv=None):
@@ -198,9 +262,11 @@ def main(argv=None):
 
     for p in sources:
         if p.suffix.lower() in VID_SUFFIXES:
-            run_video(model, p, savedir, device, args.show_split)
+            run_video(model, p, savedir, device, args.show_split,
+                      args.report_quality)
         elif p.suffix.lower() in IM_SUFFIXES:
-            run_image(model, p, savedir, device, args.show_split)
+            run_image(model, p, savedir, device, args.show_split,
+                      args.report_quality)
         else:
             print(f"Skipping unrecognized suffix: {p}", file=sys.stderr)
 

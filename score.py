@@ -2,12 +2,17 @@
 score.py (/root/reference/score.py:84-177): rebuilds the seed-dependent
 train/val split, loads --weights, runs eval over the val split, prints the
 metrics dict.
+
+--no-ref DIR scores a folder of images that have no reference instead: mean
+no-reference UIQM and UCIQE (waternet_amd.utils.nr_metrics) over the images
+in DIR. It needs no dataset, no reference images and no weights.
 """
 
 import argparse
 from pathlib import Path
 from pprint import pprint
 
+import numpy as np
 import torch
 
 from waternet_amd.data.dataset import SyntheticUIEBDataset, UIEBDataset
@@ -18,7 +23,12 @@ from waternet_amd.models.waternet import WaterNet
 
 def parse_args(argv=None):
     parser = argparse.ArgumentParser()
-    parser.add_argument("--weights", type=str, required=True)
+    # required unless --no-ref is given (checked below)
+    parser.add_argument("--weights", type=str, default=None)
+    parser.add_argument("--no-ref", type=str, default=None, metavar="DIR",
+                        help="mean no-reference UIQM/UCIQE over the images "
+                             "in DIR; needs no dataset, references or "
+                             "weights")
     # accepted-but-unused, as the reference (score.py:99-101: scoring takes
     # no epochs; the flag exists there and must keep parsing here)
     parser.add_argument("--epochs", type=int, default=400,
@@ -37,11 +47,52 @@ def parse_args(argv=None):
                         help="DataLoader workers for the val loader "
                              "(parallelizes the CPU preprocess on the "
                              "eager engine; reference default 0)")
-    return parser.parse_args(argv)
+    args = parser.parse_args(argv)
+    if args.weights is None and args.no_ref is None:
+        parser.error("the following arguments are required: --weights")
+    return args
+
+
+def score_no_ref(dirpath):
+    """Mean UIQM / UCIQE and image count over the images in dirpath; on a
+    GPU with the native extension the HIP kernels score them."""
+    from PIL import Image
+
+    from inference import IM_SUFFIXES
+    from waternet_amd.ops import native_available
+    from waternet_amd.utils.nr_metrics import KEYS, nr_metrics
+
+    root = Path(dirpath)
+    if not root.is_dir():
+        raise SystemExit(f"--no-ref: {dirpath} is not a directory")
+    paths = sorted(p for p in root.iterdir()
+                   if p.suffix.lower() in IM_SUFFIXES)
+    if not paths:
+        raise SystemExit(f"--no-ref: no images found in {dirpath}")
+    on_gpu = torch.cuda.is_available() and native_available()
+    total = None
+    for p in paths:
+        with Image.open(p) as im:
+            rgb = np.ascontiguousarray(im.convert("RGB"))
+        if on_gpu:
+            m = nr_metrics(torch.from_numpy(rgb).unsqueeze(0).cuda())
+        else:
+            m = nr_metrics(rgb)
+        total = m if total is None else total + m
+    if on_gpu:
+        total = total.cpu().numpy()
+    mean = total[0] / len(paths)
+    metrics = {"uiqm": float(mean[KEYS.index("uiqm")]),
+               "uciqe": float(mean[KEYS.index("uciqe")]),
+               "images": len(paths)}
+    pprint(metrics)
+    return metrics
 
 
 def main(argv=None):
     args = parse_args(argv)
+    if args.no_ref is not None:
+        return score_no_ref(args.no_ref)
     torch.manual_seed(0)
     if args.seed is not None:
         torch.manual_seed(args.seed)

@@ -27,6 +27,7 @@ sources = [
     str(CSRC / "pool.hip"),
     str(CSRC / "ssim.hip"),
     str(CSRC / "preprocess.hip"),
+    str(CSRC / "nr_metrics.hip"),
 ]
 
 setup(

@@ -77,6 +77,10 @@ at::Tensor ssim_sum_nhwc(const at::Tensor& a, const at::Tensor& b,
 
 // preprocess.hip
 std::vector<at::Tensor> preprocess_all(const at::Tensor& raw_u8);
+at::Tensor rgb2lab_u8(const at::Tensor& rgb_u8);
+
+// nr_metrics.hip
+at::Tensor nr_metrics(const at::Tensor& rgb_u8);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_fwd", &conv2d_fwd,
@@ -125,4 +129,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ssim_sum", &ssim_sum);
   m.def("ssim_sum_nhwc", &ssim_sum_nhwc);
   m.def("preprocess_all", &preprocess_all);
+  m.def("rgb2lab_u8", &rgb2lab_u8,
+        "uint8 NHW3 RGB -> uint8 NHW3 LAB (OpenCV 8-bit scaling)");
+  m.def("nr_metrics", &nr_metrics,
+        "uint8 NHW3 RGB -> (N,5) float64 [uicm, uism, uiconm, uiqm, uciqe]");
 }

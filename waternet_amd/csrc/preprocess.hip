@@ -184,6 +184,24 @@ __global__ void k_rgb2lab(const uint8_t* __restrict__ rgb,
   }
 }
 
+// k_rgb2lab on its own: the 8-bit LAB image UCIQE is defined on
+// (nr_metrics.hip), also bound for the tests.
+at::Tensor rgb2lab_u8(const at::Tensor& rgb_u8) {
+  TORCH_CHECK(rgb_u8.is_cuda() && rgb_u8.dtype() == at::kByte &&
+              rgb_u8.dim() == 4 && rgb_u8.size(3) == 3,
+              "rgb must be (N,H,W,3) uint8 CUDA");
+  auto rgb = rgb_u8.contiguous();
+  auto lab = at::empty_like(rgb);
+  const long total = rgb.numel() / 3;
+  if (total == 0) return lab;
+  hipLaunchKernelGGL(k_rgb2lab,
+                     dim3(std::min<long>(4096, (total + 255) / 256)),
+                     dim3(256), 0, cur_stream(), rgb.data_ptr<uint8_t>(),
+                     lab.data_ptr<uint8_t>(), total);
+  HIP_CHECK_LAST();
+  return lab;
+}
+
 // ---------------------------------------------------------------------------
 // CLAHE on the L channel: per-tile histograms -> clipped LUTs -> bilinear
 // interpolation fused with LAB->RGB.

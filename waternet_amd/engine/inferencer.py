@@ -96,3 +96,24 @@ class InferenceEngine:
         else:
             self._body()
         return self.out_static[0].cpu().numpy()
+
+    @torch.no_grad()
+    def frame_quality(self, h=None, w=None) -> torch.Tensor:
+        """No-reference quality of the last frame: a (2,5) float64 device
+        tensor [uicm, uism, uiconm, uiqm, uciqe], row 0 the uploaded frame
+        (before), row 1 the enhanced one (after), both cropped to [:h, :w]
+        so a padded engine scores only real pixels. Runs eagerly after the
+        replay; the captured graph does not contain it."""
+        from waternet_amd.utils.nr_metrics import nr_metrics
+
+        if self.out_static is None:
+            raise RuntimeError("frame_quality() needs a frame: call "
+                               "infer_frame() first")
+        h = self.h if h is None else h
+        w = self.w if w is None else w
+        if not (0 < h <= self.h and 0 < w <= self.w):
+            raise ValueError(f"crop {h}x{w} outside the {self.h}x{self.w} "
+                             "engine")
+        pair = torch.cat([self.raw_static[:, :h, :w],
+                          self.out_static[:, :h, :w]])
+        return nr_metrics(pair)
