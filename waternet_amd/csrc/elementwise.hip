@@ -1,34 +1,165 @@
 // Fused elementwise / layout / reduction kernels for the WaterNet engine
 // (gfx950). Covers SURVEY §2.2 K1/K10/K11 (cat/split folding via the input
 // builders), K15 (gated fusion fwd/bwd), K16 (ImageNet normalize), K18/K19
-// (fused squared-diff reductions), K23/K25 (fused flat Adam), plus the
-// NCHW fp32 <-> NHWC bf16 bridges and activation backward.
+// (fused squared-diff reductions), K23/K25 (fused flat Adam), K27 (uint8
+// postprocess), plus the NCHW fp32 <-> NHWC bf16 bridges and activation
+// backward.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
 #include "common.h"
 #include "gather_augment.h"
-
-namespace {
-inline hipStream_t cur_stream() { return at::cuda::getCurrentHIPStream(); }
-constexpr int TPB = 256;
-inline int grid1d(long n, int tpb = TPB, int cap = 4096) {
-  return (int)std::min<long>(cap, (n + tpb - 1) / tpb);
-}
-// The kernels below index raw data_ptr()s as dense arrays: a tensor they are
-// handed is a contiguous bf16 tensor on the GPU.
-inline bool dense_bf16(const at::Tensor& t) {
-  return t.is_cuda() && t.dtype() == at::kBFloat16 && t.is_contiguous();
-}
-}  // namespace
+#include "host_check.h"
 
 // ---------------------------------------------------------------------------
-// Input builders: 4x NCHW fp32 (3ch) -> cmg input (N,H,W,16) and three
-// refiner inputs (N,H,W,16), bf16, /1 scale (inputs already in [0,1]).
-// Folds the reference's torch.cat calls (net.py:46, net.py:76) into one pass.
+// RGB pixel family. A pixel p of N*H*W holds three logical values in one of
+// three layouts; an accessor loads or stores them as fp32:
+//   U8     (N,H,W,3) uint8
+//   Planar (N,3,H,W) fp32
+//   Nhwc   (N,H,W,Cp) bf16, Cp >= 3; a store zero-fills channels 3..Cp-1
+// A per-channel op sits between load and store. pixel_map_body serves the
+// seven layout / normalize / postprocess kernels, build_inputs_body the two
+// input builders; the __global__s below only name an instantiation.
 // ---------------------------------------------------------------------------
 
+struct SrcU8 {
+  const uint8_t* __restrict__ x;
+  WN_DEVFN void load(long p, float v[3]) const {
+    const uint8_t* s = x + p * 3;
+    v[0] = s[0]; v[1] = s[1]; v[2] = s[2];
+  }
+};
+struct SrcPlanar {
+  const float* __restrict__ x;
+  long HW;
+  WN_DEVFN void load(long p, float v[3]) const {
+    const long n = p / HW, rem = p - n * HW;
+    const float* s = x + (n * 3) * HW + rem;
+    v[0] = s[0]; v[1] = s[HW]; v[2] = s[2 * HW];
+  }
+};
+struct SrcNhwc {
+  const bf16_t* __restrict__ x;
+  int Cp;
+  WN_DEVFN void load(long p, float v[3]) const {
+    const bf16_t* s = x + p * Cp;
+    v[0] = bf2f(s[0]); v[1] = bf2f(s[1]); v[2] = bf2f(s[2]);
+  }
+};
+
+struct DstU8 {  // truncating cast: ten2arr semantics
+  uint8_t* __restrict__ y;
+  WN_DEVFN void store(long p, const float v[3]) const {
+    uint8_t* d = y + p * 3;
+    d[0] = (uint8_t)v[0]; d[1] = (uint8_t)v[1]; d[2] = (uint8_t)v[2];
+  }
+};
+struct DstPlanar {
+  float* __restrict__ y;
+  long HW;
+  WN_DEVFN void store(long p, const float v[3]) const {
+    const long n = p / HW, rem = p - n * HW;
+    float* d = y + (n * 3) * HW + rem;
+    d[0] = v[0]; d[HW] = v[1]; d[2 * HW] = v[2];
+  }
+};
+struct DstNhwc {
+  bf16_t* __restrict__ y;
+  int Cp;
+  WN_DEVFN void store(long p, const float v[3]) const {
+    bf16_t* d = y + p * Cp;
+    d[0] = f2bf(v[0]); d[1] = f2bf(v[1]); d[2] = f2bf(v[2]);
+    for (int c = 3; c < Cp; ++c) d[c] = f2bf(0.f);
+  }
+};
+
+__constant__ float IMNET_MEAN[3] = {0.485f, 0.456f, 0.406f};
+__constant__ float IMNET_STD[3] = {0.229f, 0.224f, 0.225f};
+
+struct OpIdentity {
+  WN_DEVFN float operator()(float v, int) const { return v; }
+};
+struct OpScale255 {  // uint8 -> [0,1]: a multiply by the fp32 constant
+  WN_DEVFN float operator()(float v, int) const { return v * (1.f / 255.f); }
+};
+struct OpNormFwd {  // ImageNet normalize (train.py:111-116)
+  WN_DEVFN float operator()(float v, int c) const {
+    return (v - IMNET_MEAN[c]) / IMNET_STD[c];
+  }
+};
+struct OpNormBwd {
+  WN_DEVFN float operator()(float g, int c) const { return g / IMNET_STD[c]; }
+};
+struct OpClip255 {  // clip to [0,1], *255 (training_utils.py:27-43)
+  WN_DEVFN float operator()(float v, int) const {
+    return fminf(fmaxf(v, 0.f), 1.f) * 255.f;
+  }
+};
+
+template <class Src, class Op>
+WN_DEVFN void load_rgb(const Src& src, Op op, long p, float v[3]) {
+  src.load(p, v);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) v[c] = op(v[c], c);
+}
+
+// A thread's walk of a grid-stride loop. The __global__ passes its own
+// blockDim.x: the compiler folds that read to the launch's uniform block
+// size only in the kernel function itself; inside a device function, even a
+// forceinline one, it becomes a dependent global load in the prologue.
+struct GridStride {
+  long first, step;
+};
+WN_DEVFN GridStride grid_stride(unsigned block_dim) {
+  return {(long)blockIdx.x * block_dim + threadIdx.x,
+          (long)gridDim.x * block_dim};
+}
+
+template <class Src, class Dst, class Op>
+WN_DEVFN void pixel_map_body(GridStride t, Src src, Dst dst, Op op,
+                             long NHW) {
+  for (long p = t.first; p < NHW; p += t.step) {
+    float v[3];
+    load_rgb(src, op, p, v);
+    dst.store(p, v);
+  }
+}
+
+// Input builders: four RGB sources -> cmg input [raw wb ce gc 0000] and the
+// three refiner inputs [raw src 0...], all (N,H,W,16) bf16. Folds the
+// reference's torch.cat calls (net.py:46, net.py:76) into one pass.
+template <class Src, class Op>
+WN_DEVFN void build_inputs_body(GridStride t, Src raw, Src wb, Src ce,
+                                Src gc, Op op, bf16_t* __restrict__ cmg_in,
+                                bf16_t* __restrict__ rwb_in,
+                                bf16_t* __restrict__ rce_in,
+                                bf16_t* __restrict__ rgc_in, long NHW) {
+  for (long p = t.first; p < NHW; p += t.step) {
+    float r[3], w[3], c[3], g[3];
+    load_rgb(raw, op, p, r);
+    load_rgb(wb, op, p, w);
+    load_rgb(ce, op, p, c);
+    load_rgb(gc, op, p, g);
+    auto put3 = [](bf16_t* q, const float a[3]) {
+      q[0] = f2bf(a[0]); q[1] = f2bf(a[1]); q[2] = f2bf(a[2]);
+    };
+    bf16_t* o = cmg_in + p * 16;
+    put3(o, r); put3(o + 3, w); put3(o + 6, c); put3(o + 9, g);
+    o[12] = o[13] = o[14] = o[15] = f2bf(0.f);
+    auto emit = [&](bf16_t* dst, const float a[3]) {
+      bf16_t* q = dst + p * 16;
+      put3(q, r); put3(q + 3, a);
+#pragma unroll
+      for (int i = 6; i < 16; ++i) q[i] = f2bf(0.f);
+    };
+    emit(rwb_in, w);
+    emit(rce_in, c);
+    emit(rgc_in, g);
+  }
+}
+
+// 4x NCHW fp32 (3ch, already in [0,1])
 __global__ void k_build_inputs(const float* __restrict__ raw,
                                const float* __restrict__ wb,
                                const float* __restrict__ ce,
@@ -38,38 +169,14 @@ __global__ void k_build_inputs(const float* __restrict__ raw,
                                bf16_t* __restrict__ rce_in,
                                bf16_t* __restrict__ rgc_in, long NHW,
                                long HW) {
-  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < NHW;
-       p += (long)gridDim.x * blockDim.x) {
-    const long n = p / HW, rem = p - n * HW;
-    const long base = n * 3 * HW + rem;
-    float r0 = raw[base], r1 = raw[base + HW], r2 = raw[base + 2 * HW];
-    float w0 = wb[base], w1 = wb[base + HW], w2 = wb[base + 2 * HW];
-    float c0 = ce[base], c1 = ce[base + HW], c2 = ce[base + 2 * HW];
-    float g0 = gc[base], g1 = gc[base + HW], g2 = gc[base + 2 * HW];
-    bf16_t* o = cmg_in + p * 16;
-    o[0] = f2bf(r0); o[1] = f2bf(r1); o[2] = f2bf(r2);
-    o[3] = f2bf(w0); o[4] = f2bf(w1); o[5] = f2bf(w2);
-    o[6] = f2bf(c0); o[7] = f2bf(c1); o[8] = f2bf(c2);
-    o[9] = f2bf(g0); o[10] = f2bf(g1); o[11] = f2bf(g2);
-    o[12] = o[13] = o[14] = o[15] = f2bf(0.f);
-    auto emit = [&](bf16_t* dst, float a0, float a1, float a2) {
-      bf16_t* q = dst + p * 16;
-      q[0] = f2bf(r0); q[1] = f2bf(r1); q[2] = f2bf(r2);
-      q[3] = f2bf(a0); q[4] = f2bf(a1); q[5] = f2bf(a2);
-#pragma unroll
-      for (int i = 6; i < 16; ++i) q[i] = f2bf(0.f);
-    };
-    emit(rwb_in, w0, w1, w2);
-    emit(rce_in, c0, c1, c2);
-    emit(rgc_in, g0, g1, g2);
-  }
+  build_inputs_body(grid_stride(blockDim.x), SrcPlanar{raw, HW},
+                    SrcPlanar{wb, HW}, SrcPlanar{ce, HW}, SrcPlanar{gc, HW},
+                    OpIdentity{}, cmg_in, rwb_in, rce_in, rgc_in, NHW);
 }
 
-// uint8 variant: builds the same four conv inputs straight from the uint8
-// HWC batch tensors (raw + the GPU-preprocess outputs), /255 — removes the
-// per-tensor u8->NCHW-fp32 bridges and the NCHW intermediates entirely
-// (full-NHWC training path; reference arr2ten training_utils.py:11-27 +
-// torch.cat net.py:46/76 in ONE kernel).
+// straight from the uint8 HWC batch tensors (raw + the GPU-preprocess
+// outputs), /255: no u8->NCHW-fp32 bridges and no NCHW intermediates on the
+// full-NHWC training path (reference arr2ten training_utils.py:11-27)
 __global__ void k_build_inputs_u8(const uint8_t* __restrict__ raw,
                                   const uint8_t* __restrict__ wb,
                                   const uint8_t* __restrict__ ce,
@@ -78,46 +185,61 @@ __global__ void k_build_inputs_u8(const uint8_t* __restrict__ raw,
                                   bf16_t* __restrict__ rwb_in,
                                   bf16_t* __restrict__ rce_in,
                                   bf16_t* __restrict__ rgc_in, long NHW) {
-  constexpr float S = 1.f / 255.f;
-  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < NHW;
-       p += (long)gridDim.x * blockDim.x) {
-    const long s = p * 3;
-    float r0 = raw[s] * S, r1 = raw[s + 1] * S, r2 = raw[s + 2] * S;
-    float w0 = wb[s] * S, w1 = wb[s + 1] * S, w2 = wb[s + 2] * S;
-    float c0 = ce[s] * S, c1 = ce[s + 1] * S, c2 = ce[s + 2] * S;
-    float g0 = gc[s] * S, g1 = gc[s + 1] * S, g2 = gc[s + 2] * S;
-    bf16_t* o = cmg_in + p * 16;
-    o[0] = f2bf(r0); o[1] = f2bf(r1); o[2] = f2bf(r2);
-    o[3] = f2bf(w0); o[4] = f2bf(w1); o[5] = f2bf(w2);
-    o[6] = f2bf(c0); o[7] = f2bf(c1); o[8] = f2bf(c2);
-    o[9] = f2bf(g0); o[10] = f2bf(g1); o[11] = f2bf(g2);
-    o[12] = o[13] = o[14] = o[15] = f2bf(0.f);
-    auto emit = [&](bf16_t* dst, float a0, float a1, float a2) {
-      bf16_t* q = dst + p * 16;
-      q[0] = f2bf(r0); q[1] = f2bf(r1); q[2] = f2bf(r2);
-      q[3] = f2bf(a0); q[4] = f2bf(a1); q[5] = f2bf(a2);
-#pragma unroll
-      for (int i = 6; i < 16; ++i) q[i] = f2bf(0.f);
-    };
-    emit(rwb_in, w0, w1, w2);
-    emit(rce_in, c0, c1, c2);
-    emit(rgc_in, g0, g1, g2);
-  }
+  build_inputs_body(grid_stride(blockDim.x), SrcU8{raw}, SrcU8{wb},
+                    SrcU8{ce}, SrcU8{gc}, OpScale255{}, cmg_in, rwb_in, rce_in,
+                    rgc_in, NHW);
 }
 
-// uint8 HWC -> (N,H,W,Cp) bf16 [0,1] (the ref tensor for the NHWC loss path)
+// uint8 HWC -> (N,H,W,Cp) bf16 [0,1] (the ref tensor of the NHWC loss path)
 __global__ void k_u8_to_nhwc(const uint8_t* __restrict__ x,
                              bf16_t* __restrict__ y, long NHW, int Cp) {
-  constexpr float S = 1.f / 255.f;
-  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < NHW;
-       p += (long)gridDim.x * blockDim.x) {
-    const uint8_t* s = x + p * 3;
-    bf16_t* d = y + (long)p * Cp;
-    d[0] = f2bf(s[0] * S);
-    d[1] = f2bf(s[1] * S);
-    d[2] = f2bf(s[2] * S);
-    for (int c = 3; c < Cp; ++c) d[c] = f2bf(0.f);
-  }
+  pixel_map_body(grid_stride(blockDim.x), SrcU8{x}, DstNhwc{y, Cp},
+                 OpScale255{}, NHW);
+}
+
+// uint8 HWC -> NCHW fp32 [0,1] input bridge
+__global__ void k_u8_to_nchw(const uint8_t* __restrict__ x,
+                             float* __restrict__ y, long NHW, long HW) {
+  pixel_map_body(grid_stride(blockDim.x), SrcU8{x}, DstPlanar{y, HW},
+                 OpScale255{}, NHW);
+}
+
+// Fused postprocess (K27): NHWC bf16 model output -> uint8 RGB
+__global__ void k_out_to_u8(const bf16_t* __restrict__ x,
+                            uint8_t* __restrict__ y, long NHW, int Cp) {
+  pixel_map_body(grid_stride(blockDim.x), SrcNhwc{x, Cp}, DstU8{y},
+                 OpClip255{}, NHW);
+}
+
+// ImageNet normalize fused with NCHW fp32 -> NHWC bf16, and its backward
+__global__ void k_normalize_vgg_fwd(const float* __restrict__ x,
+                                    bf16_t* __restrict__ y, long NHW,
+                                    long HW, int Cp) {
+  pixel_map_body(grid_stride(blockDim.x), SrcPlanar{x, HW}, DstNhwc{y, Cp},
+                 OpNormFwd{}, NHW);
+}
+
+__global__ void k_normalize_vgg_bwd(const bf16_t* __restrict__ dy,
+                                    float* __restrict__ dx, long NHW,
+                                    long HW, int Cp) {
+  pixel_map_body(grid_stride(blockDim.x), SrcNhwc{dy, Cp}, DstPlanar{dx, HW},
+                 OpNormBwd{}, NHW);
+}
+
+// In-layout normalize (full-NHWC loss path: the WaterNet output and ref stay
+// NHWC from the fusion kernel through the VGG towers, no NCHW round trip)
+__global__ void k_normalize_nhwc_fwd(const bf16_t* __restrict__ x,
+                                     bf16_t* __restrict__ y, long NHW,
+                                     int Cp) {
+  pixel_map_body(grid_stride(blockDim.x), SrcNhwc{x, Cp}, DstNhwc{y, Cp},
+                 OpNormFwd{}, NHW);
+}
+
+__global__ void k_normalize_nhwc_bwd(const bf16_t* __restrict__ dy,
+                                     bf16_t* __restrict__ dx, long NHW,
+                                     int Cp) {
+  pixel_map_body(grid_stride(blockDim.x), SrcNhwc{dy, Cp}, DstNhwc{dx, Cp},
+                 OpNormBwd{}, NHW);
 }
 
 // ---------------------------------------------------------------------------
@@ -250,6 +372,10 @@ __global__ void k_fusion_bwd(const bf16_t* __restrict__ dout,
 // Activation backward: dpre = dY * act'(Y)  (Y = post-activation output)
 // ---------------------------------------------------------------------------
 
+WN_DEVFN float act_grad(float g, float v, int act) {
+  return (act == ACT_RELU) ? (v > 0.f ? g : 0.f) : g * v * (1.f - v);
+}
+
 __global__ void k_act_bwd(const bf16_t* __restrict__ dy,
                           const bf16_t* __restrict__ y,
                           bf16_t* __restrict__ dpre, long n, int act) {
@@ -262,19 +388,13 @@ __global__ void k_act_bwd(const bf16_t* __restrict__ dy,
     const bf16x8 vv = *reinterpret_cast<const bf16x8*>(y + i * 8);
     bf16x8 r;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float g = bf2f(gv[e]), v = bf2f(vv[e]);
-      r[e] = f2bf((act == ACT_RELU) ? (v > 0.f ? g : 0.f)
-                                    : g * v * (1.f - v));
-    }
+    for (int e = 0; e < 8; ++e)
+      r[e] = f2bf(act_grad(bf2f(gv[e]), bf2f(vv[e]), act));
     *reinterpret_cast<bf16x8*>(dpre + i * 8) = r;
   }
   for (long i = n8 * 8 + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (long)gridDim.x * blockDim.x) {
-    const float g = bf2f(dy[i]), v = bf2f(y[i]);
-    dpre[i] = f2bf((act == ACT_RELU) ? (v > 0.f ? g : 0.f)
-                                     : g * v * (1.f - v));
-  }
+       i += (long)gridDim.x * blockDim.x)
+    dpre[i] = f2bf(act_grad(bf2f(dy[i]), bf2f(y[i]), act));
 }
 
 // act_bwd fused with the bias-gradient column sums (K25 epilogue fusion):
@@ -302,9 +422,7 @@ __global__ void k_act_bwd_bias(const bf16_t* __restrict__ dy,
     bf16x8 r;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float g = bf2f(gv[e]), v = bf2f(vv[e]);
-      const float d = (act == ACT_RELU) ? (v > 0.f ? g : 0.f)
-                                        : g * v * (1.f - v);
+      const float d = act_grad(bf2f(gv[e]), bf2f(vv[e]), act);
       r[e] = f2bf(d);
       s[e] += d;
     }
@@ -336,73 +454,6 @@ __global__ void k_abb_reduce(const float* __restrict__ part,
     __syncthreads();
   }
   if (threadIdx.x == 0) db[k] += red[0];
-}
-
-// ---------------------------------------------------------------------------
-// ImageNet normalize fused with NCHW fp32 -> NHWC bf16 (and backward)
-// (train.py:111-116)
-// ---------------------------------------------------------------------------
-
-__constant__ float IMNET_MEAN[3] = {0.485f, 0.456f, 0.406f};
-__constant__ float IMNET_STD[3] = {0.229f, 0.224f, 0.225f};
-
-__global__ void k_normalize_vgg_fwd(const float* __restrict__ x,
-                                    bf16_t* __restrict__ y, long NHW,
-                                    long HW, int Cp) {
-  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < NHW;
-       p += (long)gridDim.x * blockDim.x) {
-    const long n = p / HW, rem = p - n * HW;
-    const float* src = x + (n * 3) * HW + rem;
-    bf16_t* dst = y + p * Cp;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      dst[c] = f2bf((src[(long)c * HW] - IMNET_MEAN[c]) / IMNET_STD[c]);
-    for (int c = 3; c < Cp; ++c) dst[c] = f2bf(0.f);
-  }
-}
-
-__global__ void k_normalize_vgg_bwd(const bf16_t* __restrict__ dy,
-                                    float* __restrict__ dx, long NHW,
-                                    long HW, int Cp) {
-  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < NHW;
-       p += (long)gridDim.x * blockDim.x) {
-    const long n = p / HW, rem = p - n * HW;
-    const bf16_t* src = dy + p * Cp;
-    float* dst = dx + (n * 3) * HW + rem;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      dst[(long)c * HW] = bf2f(src[c]) / IMNET_STD[c];
-  }
-}
-
-// NHWC bf16 -> NHWC bf16 in-layout normalize (full-NHWC loss path: the
-// WaterNet output and ref stay NHWC from the fusion kernel through the VGG
-// towers — no NCHW round trip).
-__global__ void k_normalize_nhwc_fwd(const bf16_t* __restrict__ x,
-                                     bf16_t* __restrict__ y, long NHW,
-                                     int Cp) {
-  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < NHW;
-       p += (long)gridDim.x * blockDim.x) {
-    const bf16_t* s = x + (long)p * Cp;
-    bf16_t* d = y + (long)p * Cp;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      d[c] = f2bf((bf2f(s[c]) - IMNET_MEAN[c]) / IMNET_STD[c]);
-    for (int c = 3; c < Cp; ++c) d[c] = f2bf(0.f);
-  }
-}
-
-__global__ void k_normalize_nhwc_bwd(const bf16_t* __restrict__ dy,
-                                     bf16_t* __restrict__ dx, long NHW,
-                                     int Cp) {
-  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < NHW;
-       p += (long)gridDim.x * blockDim.x) {
-    const bf16_t* s = dy + (long)p * Cp;
-    bf16_t* d = dx + (long)p * Cp;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) d[c] = f2bf(bf2f(s[c]) / IMNET_STD[c]);
-    for (int c = 3; c < Cp; ++c) d[c] = f2bf(0.f);
-  }
 }
 
 // ---------------------------------------------------------------------------
@@ -517,112 +568,244 @@ __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g,
   }
 }
 
-// ---------------------------------------------------------------------------
-// Fused postprocess (K27): NHWC bf16 model output -> uint8 RGB
-// (clip to [0,1], *255, truncate — ten2arr semantics training_utils.py:27-43)
-// and uint8 NHWC -> NCHW fp32 [0,1] input bridge.
-// ---------------------------------------------------------------------------
-
-__global__ void k_out_to_u8(const bf16_t* __restrict__ x,
-                            uint8_t* __restrict__ y, long NHW, int Cp) {
-  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < NHW;
-       p += (long)gridDim.x * blockDim.x) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      float v = bf2f(x[p * Cp + c]);
-      v = fminf(fmaxf(v, 0.f), 1.f) * 255.f;
-      y[p * 3 + c] = (uint8_t)v;
-    }
-  }
-}
-
-__global__ void k_u8_to_nchw(const uint8_t* __restrict__ x,
-                             float* __restrict__ y, long NHW, long HW) {
-  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < NHW;
-       p += (long)gridDim.x * blockDim.x) {
-    const long n = p / HW, rem = p - n * HW;
-    float* dst = y + (n * 3) * HW + rem;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      dst[(long)c * HW] = (float)x[p * 3 + c] * (1.f / 255.f);
-  }
-}
-
 // ===========================================================================
-// Host wrappers
+// Host wrappers. Every argument a kernel indexes is checked first (the
+// vocabulary is host_check.h); an empty input returns its empty result
+// without a launch; a contiguous copy lives in a named local.
 // ===========================================================================
+
+namespace {
+inline const bf16_t* cbf(const at::Tensor& t) {
+  return (const bf16_t*)t.data_ptr();
+}
+inline bf16_t* bf(at::Tensor& t) { return (bf16_t*)t.data_ptr(); }
+}  // namespace
+
+// the builders' four (N,H,W,16) bf16 outputs
+static std::vector<at::Tensor> empty_inputs(const at::Tensor& raw, long N,
+                                            long H, long W) {
+  const auto opts = raw.options().dtype(at::kBFloat16);
+  return {at::empty({N, H, W, 16}, opts), at::empty({N, H, W, 16}, opts),
+          at::empty({N, H, W, 16}, opts), at::empty({N, H, W, 16}, opts)};
+}
 
 std::vector<at::Tensor> build_inputs(const at::Tensor& raw,
                                      const at::Tensor& wb,
                                      const at::Tensor& ce,
                                      const at::Tensor& gc) {
-  TORCH_CHECK(raw.is_cuda() && raw.dtype() == at::kFloat && raw.dim() == 4 &&
-              raw.size(1) == 3, "raw must be (N,3,H,W) fp32 CUDA");
+  TORCH_CHECK(on_gpu(raw, at::kFloat, 4) && raw.size(1) == 3,
+              "build_inputs: raw must be (N,3,H,W) fp32 on the GPU");
+  TORCH_CHECK(like(wb, raw) && like(ce, raw) && like(gc, raw),
+              "build_inputs: wb, ce and gc must have raw's dtype, shape and "
+              "device");
+  const auto r = raw.contiguous(), w = wb.contiguous(), c = ce.contiguous(),
+             g = gc.contiguous();
   const long N = raw.size(0), H = raw.size(2), W = raw.size(3);
-  const long NHW = N * H * W, HW = H * W;
-  auto opts = raw.options().dtype(at::kBFloat16);
-  auto cmg_in = at::empty({N, H, W, 16}, opts);
-  auto rwb = at::empty({N, H, W, 16}, opts);
-  auto rce = at::empty({N, H, W, 16}, opts);
-  auto rgc = at::empty({N, H, W, 16}, opts);
-  hipLaunchKernelGGL(k_build_inputs, dim3(grid1d(NHW)), dim3(TPB), 0,
-                     cur_stream(), raw.contiguous().data_ptr<float>(),
-                     wb.contiguous().data_ptr<float>(),
-                     ce.contiguous().data_ptr<float>(),
-                     gc.contiguous().data_ptr<float>(),
-                     (bf16_t*)cmg_in.data_ptr(), (bf16_t*)rwb.data_ptr(),
-                     (bf16_t*)rce.data_ptr(), (bf16_t*)rgc.data_ptr(), NHW,
-                     HW);
-  HIP_CHECK_LAST();
-  return {cmg_in, rwb, rce, rgc};
+  auto out = empty_inputs(raw, N, H, W);
+  launch1d(k_build_inputs, N * H * W, r.data_ptr<float>(),
+           w.data_ptr<float>(), c.data_ptr<float>(), g.data_ptr<float>(),
+           bf(out[0]), bf(out[1]), bf(out[2]), bf(out[3]), N * H * W, H * W);
+  return out;
 }
 
 std::vector<at::Tensor> build_inputs_u8(const at::Tensor& raw,
                                         const at::Tensor& wb,
                                         const at::Tensor& ce,
                                         const at::Tensor& gc) {
-  TORCH_CHECK(raw.is_cuda() && raw.dtype() == at::kByte && raw.dim() == 4 &&
-              raw.size(3) == 3, "raw must be (N,H,W,3) uint8 CUDA");
+  TORCH_CHECK(on_gpu(raw, at::kByte, 4) && raw.size(3) == 3,
+              "build_inputs_u8: raw must be (N,H,W,3) uint8 on the GPU");
+  TORCH_CHECK(like(wb, raw) && like(ce, raw) && like(gc, raw),
+              "build_inputs_u8: wb, ce and gc must have raw's dtype, shape "
+              "and device");
+  const auto r = raw.contiguous(), w = wb.contiguous(), c = ce.contiguous(),
+             g = gc.contiguous();
   const long N = raw.size(0), H = raw.size(1), W = raw.size(2);
-  const long NHW = N * H * W;
-  auto opts = raw.options().dtype(at::kBFloat16);
-  auto cmg_in = at::empty({N, H, W, 16}, opts);
-  auto rwb = at::empty({N, H, W, 16}, opts);
-  auto rce = at::empty({N, H, W, 16}, opts);
-  auto rgc = at::empty({N, H, W, 16}, opts);
-  hipLaunchKernelGGL(k_build_inputs_u8, dim3(grid1d(NHW)), dim3(TPB), 0,
-                     cur_stream(), raw.contiguous().data_ptr<uint8_t>(),
-                     wb.contiguous().data_ptr<uint8_t>(),
-                     ce.contiguous().data_ptr<uint8_t>(),
-                     gc.contiguous().data_ptr<uint8_t>(),
-                     (bf16_t*)cmg_in.data_ptr(), (bf16_t*)rwb.data_ptr(),
-                     (bf16_t*)rce.data_ptr(), (bf16_t*)rgc.data_ptr(), NHW);
-  HIP_CHECK_LAST();
-  return {cmg_in, rwb, rce, rgc};
+  auto out = empty_inputs(raw, N, H, W);
+  launch1d(k_build_inputs_u8, N * H * W, r.data_ptr<uint8_t>(),
+           w.data_ptr<uint8_t>(), c.data_ptr<uint8_t>(),
+           g.data_ptr<uint8_t>(), bf(out[0]), bf(out[1]), bf(out[2]),
+           bf(out[3]), N * H * W);
+  return out;
 }
 
 at::Tensor u8_to_nhwc(const at::Tensor& x, int64_t Cp) {
-  TORCH_CHECK(x.is_cuda() && x.dtype() == at::kByte && x.dim() == 4 &&
-              x.size(3) == 3);
+  TORCH_CHECK(on_gpu(x, at::kByte, 4) && x.size(3) == 3,
+              "u8_to_nhwc: x must be (N,H,W,3) uint8 on the GPU");
+  TORCH_CHECK(has_rgb(Cp), "u8_to_nhwc: Cp must be at least 3");
+  const auto xc = x.contiguous();
   const long N = x.size(0), H = x.size(1), W = x.size(2);
   auto y = at::empty({N, H, W, Cp}, x.options().dtype(at::kBFloat16));
+  launch1d(k_u8_to_nhwc, N * H * W, xc.data_ptr<uint8_t>(), bf(y), N * H * W,
+           (int)Cp);
+  return y;
+}
+
+at::Tensor u8_to_nchw(const at::Tensor& x) {
+  TORCH_CHECK(on_gpu(x, at::kByte, 4) && x.size(3) == 3,
+              "u8_to_nchw: x must be (N,H,W,3) uint8 on the GPU");
+  const auto xc = x.contiguous();
+  const long N = x.size(0), H = x.size(1), W = x.size(2);
+  auto y = at::empty({N, 3, H, W}, x.options().dtype(at::kFloat));
+  launch1d(k_u8_to_nchw, N * H * W, xc.data_ptr<uint8_t>(),
+           y.data_ptr<float>(), N * H * W, H * W);
+  return y;
+}
+
+// checks x: (N,H,W,Cp >= 3) bf16 on the GPU, any strides (the caller takes
+// the contiguous copy); returns its pixel count
+static long rgb_nhwc_pixels(const char* name, const at::Tensor& x) {
+  TORCH_CHECK(on_gpu(x, at::kBFloat16, 4) && has_rgb(x.size(3)), name,
+              ": the tensor must be (N,H,W,Cp >= 3) bf16 on the GPU");
+  return x.size(0) * x.size(1) * x.size(2);
+}
+
+at::Tensor out_to_u8(const at::Tensor& x) {
+  const long NHW = rgb_nhwc_pixels("out_to_u8", x);
+  const auto xc = x.contiguous();
+  auto y = at::empty({x.size(0), x.size(1), x.size(2), 3},
+                     x.options().dtype(at::kByte));
+  launch1d(k_out_to_u8, NHW, cbf(xc), y.data_ptr<uint8_t>(), NHW,
+           (int)x.size(3));
+  return y;
+}
+
+at::Tensor normalize_nhwc_fwd(const at::Tensor& x) {
+  const long NHW = rgb_nhwc_pixels("normalize_nhwc_fwd", x);
+  const auto xc = x.contiguous();
+  auto y = at::empty_like(xc);
+  launch1d(k_normalize_nhwc_fwd, NHW, cbf(xc), bf(y), NHW, (int)x.size(3));
+  return y;
+}
+
+at::Tensor normalize_nhwc_bwd(const at::Tensor& dy) {
+  const long NHW = rgb_nhwc_pixels("normalize_nhwc_bwd", dy);
+  const auto dyc = dy.contiguous();
+  auto dx = at::empty_like(dyc);
+  launch1d(k_normalize_nhwc_bwd, NHW, cbf(dyc), bf(dx), NHW,
+           (int)dy.size(3));
+  return dx;
+}
+
+at::Tensor normalize_vgg_fwd(const at::Tensor& x, int64_t Cp) {
+  TORCH_CHECK(on_gpu(x, at::kFloat, 4) && x.size(1) == 3,
+              "normalize_vgg_fwd: x must be (N,3,H,W) fp32 on the GPU");
+  TORCH_CHECK(has_rgb(Cp), "normalize_vgg_fwd: Cp must be at least 3");
+  const auto xc = x.contiguous();
+  const long N = x.size(0), H = x.size(2), W = x.size(3);
+  auto y = at::empty({N, H, W, Cp}, x.options().dtype(at::kBFloat16));
+  launch1d(k_normalize_vgg_fwd, N * H * W, xc.data_ptr<float>(), bf(y),
+           N * H * W, H * W, (int)Cp);
+  return y;
+}
+
+at::Tensor normalize_vgg_bwd(const at::Tensor& dy, int64_t C) {
+  TORCH_CHECK(C == 3, "normalize_vgg_bwd: C must be 3");
+  const long NHW = rgb_nhwc_pixels("normalize_vgg_bwd", dy);
+  const auto dyc = dy.contiguous();
+  const long H = dy.size(1), W = dy.size(2);
+  auto dx = at::empty({dy.size(0), C, H, W}, dy.options().dtype(at::kFloat));
+  launch1d(k_normalize_vgg_bwd, NHW, cbf(dyc), dx.data_ptr<float>(), NHW,
+           H * W, (int)dy.size(3));
+  return dx;
+}
+
+// grid of the LDS-tiled bridges: 256 pixels x 16 channels per block
+static dim3 bridge_grid(long NHW, long Cp) {
+  return dim3((unsigned)((NHW + 255) / 256), 1, (unsigned)(Cp / 16));
+}
+
+at::Tensor nchw_to_nhwc(const at::Tensor& x, int64_t Cp) {
+  TORCH_CHECK(on_gpu(x, at::kFloat, 4),
+              "nchw_to_nhwc: x must be (N,C,H,W) fp32 on the GPU");
+  const long N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  TORCH_CHECK(bridge_channels(C, Cp),
+              "nchw_to_nhwc: Cp must be a positive multiple of 16 and at "
+              "least C");
+  const auto xc = x.contiguous();
+  auto y = at::empty({N, H, W, Cp}, x.options().dtype(at::kBFloat16));
   const long NHW = N * H * W;
-  hipLaunchKernelGGL(k_u8_to_nhwc, dim3(grid1d(NHW)), dim3(TPB), 0,
-                     cur_stream(), x.contiguous().data_ptr<uint8_t>(),
-                     (bf16_t*)y.data_ptr(), NHW, (int)Cp);
+  if (NHW == 0) return y;
+  hipLaunchKernelGGL(k_nchw2nhwc, bridge_grid(NHW, Cp), dim3(256), 0,
+                     cur_stream(), xc.data_ptr<float>(), bf(y), NHW, H * W,
+                     (int)C, (int)Cp);
   HIP_CHECK_LAST();
   return y;
 }
 
+at::Tensor nhwc_to_nchw(const at::Tensor& x, int64_t C) {
+  TORCH_CHECK(on_gpu(x, at::kBFloat16, 4),
+              "nhwc_to_nchw: x must be (N,H,W,Cp) bf16 on the GPU");
+  const long N = x.size(0), H = x.size(1), W = x.size(2), Cp = x.size(3);
+  TORCH_CHECK(bridge_channels(C, Cp),
+              "nhwc_to_nchw: Cp must be a positive multiple of 16 and at "
+              "least C >= 0");
+  const auto xc = x.contiguous();
+  auto y = at::empty({N, C, H, W}, x.options().dtype(at::kFloat));
+  const long NHW = N * H * W;
+  if (y.numel() == 0) return y;
+  hipLaunchKernelGGL(k_nhwc2nchw, bridge_grid(NHW, Cp), dim3(256), 0,
+                     cur_stream(), cbf(xc), y.data_ptr<float>(), NHW, H * W,
+                     (int)C, (int)Cp);
+  HIP_CHECK_LAST();
+  return y;
+}
+
+at::Tensor fusion_fwd(const at::Tensor& maps, const at::Tensor& rwb,
+                      const at::Tensor& rce, const at::Tensor& rgc) {
+  TORCH_CHECK(dense(maps, at::kBFloat16, 4) && maps.size(3) == 16,
+              "fusion_fwd: maps must be contiguous (N,H,W,16) bf16 on the "
+              "GPU");
+  TORCH_CHECK(dense_like(rwb, maps) && dense_like(rce, maps) &&
+                  dense_like(rgc, maps),
+              "fusion_fwd: rwb, rce and rgc must be contiguous, of maps' "
+              "dtype, shape and device");
+  const long NHW = maps.size(0) * maps.size(1) * maps.size(2);
+  auto out = at::empty_like(maps);
+  launch1d(k_fusion_fwd, NHW, cbf(maps), cbf(rwb), cbf(rce), cbf(rgc),
+           bf(out), NHW);
+  return out;
+}
+
+std::vector<at::Tensor> fusion_bwd(const at::Tensor& dout,
+                                   const at::Tensor& maps,
+                                   const at::Tensor& rwb,
+                                   const at::Tensor& rce,
+                                   const at::Tensor& rgc) {
+  TORCH_CHECK(dense(maps, at::kBFloat16, 4) && maps.size(3) == 16,
+              "fusion_bwd: maps must be contiguous (N,H,W,16) bf16 on the "
+              "GPU");
+  TORCH_CHECK(dense_like(dout, maps) && dense_like(rwb, maps) &&
+                  dense_like(rce, maps) && dense_like(rgc, maps),
+              "fusion_bwd: dout, rwb, rce and rgc must be contiguous, of "
+              "maps' dtype, shape and device");
+  const long NHW = maps.size(0) * maps.size(1) * maps.size(2);
+  auto dmaps = at::empty_like(maps);
+  auto drwb = at::empty_like(maps);
+  auto drce = at::empty_like(maps);
+  auto drgc = at::empty_like(maps);
+  launch1d(k_fusion_bwd, NHW, cbf(dout), cbf(maps), cbf(rwb), cbf(rce),
+           cbf(rgc), bf(dmaps), bf(drwb), bf(drce), bf(drgc), NHW);
+  return {dmaps, drwb, drce, drgc};
+}
+
+at::Tensor act_bwd(const at::Tensor& dy, const at::Tensor& y, int64_t act) {
+  TORCH_CHECK(dense(dy, at::kBFloat16) && dense_like(y, dy),
+              "act_bwd: dy and y must be contiguous bf16 on the GPU, of one "
+              "shape and device");
+  TORCH_CHECK(act == ACT_RELU || act == ACT_SIGMOID,
+              "act_bwd: act must be relu (1) or sigmoid (2)");
+  auto dpre = at::empty_like(dy);
+  const long n = dy.numel();
+  launch1d(k_act_bwd, (n + 7) / 8, cbf(dy), cbf(y), bf(dpre), n, (int)act);
+  return dpre;
+}
+
 at::Tensor act_bwd_bias(const at::Tensor& dy, const at::Tensor& y,
                         int64_t act, at::Tensor& db) {
-  TORCH_CHECK(dense_bf16(dy) && dense_bf16(y) && dy.dim() == 4,
+  TORCH_CHECK(dense(dy, at::kBFloat16, 4) && dense_like(y, dy),
               "act_bwd_bias: dy and y must be contiguous (N,H,W,Kp) bf16 on "
-              "the GPU");
-  TORCH_CHECK(y.sizes() == dy.sizes() && y.device() == dy.device(),
-              "act_bwd_bias: dy and y differ in shape or device");
-  TORCH_CHECK(db.is_cuda() && db.dtype() == at::kFloat && db.dim() == 1 &&
-                  db.is_contiguous() && db.device() == dy.device(),
+              "the GPU, of one shape and device");
+  TORCH_CHECK(dense(db, at::kFloat, 1) && db.device() == dy.device(),
               "act_bwd_bias: db must be a contiguous 1-D fp32 tensor on dy's "
               "device");
   TORCH_CHECK(act == ACT_RELU || act == ACT_SIGMOID,
@@ -638,12 +821,11 @@ at::Tensor act_bwd_bias(const at::Tensor& dy, const at::Tensor& y,
   const long n8 = n / 8;
   // blocks*blockDim*8 must be divisible by Kp: 256*8 = 2048 is divisible
   // by every Kp <= 128, so any block count works
-  const int blocks = (int)std::min<long>(512, (n8 + 255) / 256);
+  const int blocks = grid1d(n8, TPB, 512);
   auto part = at::empty({blocks, (long)Kp},
                         dy.options().dtype(at::kFloat));
   hipLaunchKernelGGL(k_act_bwd_bias, dim3(blocks), dim3(TPB), 0,
-                     cur_stream(), (const bf16_t*)dy.data_ptr(),
-                     (const bf16_t*)y.data_ptr(), (bf16_t*)dpre.data_ptr(),
+                     cur_stream(), cbf(dy), cbf(y), bf(dpre),
                      part.data_ptr<float>(), n8, Kp, (int)act);
   HIP_CHECK_LAST();
   hipLaunchKernelGGL(k_abb_reduce, dim3(K), dim3(256), 0, cur_stream(),
@@ -653,249 +835,58 @@ at::Tensor act_bwd_bias(const at::Tensor& dy, const at::Tensor& y,
   return dpre;
 }
 
-at::Tensor normalize_nhwc_fwd(const at::Tensor& x) {
-  TORCH_CHECK(x.is_cuda() && x.dtype() == at::kBFloat16 && x.dim() == 4);
-  const long Cp = x.size(3);
-  const long NHW = x.numel() / Cp;
-  auto y = at::empty_like(x);
-  hipLaunchKernelGGL(k_normalize_nhwc_fwd, dim3(grid1d(NHW)), dim3(TPB), 0,
-                     cur_stream(), (const bf16_t*)x.contiguous().data_ptr(),
-                     (bf16_t*)y.data_ptr(), NHW, (int)Cp);
-  HIP_CHECK_LAST();
-  return y;
-}
-
-at::Tensor normalize_nhwc_bwd(const at::Tensor& dy) {
-  TORCH_CHECK(dy.is_cuda() && dy.dtype() == at::kBFloat16 && dy.dim() == 4);
-  const long Cp = dy.size(3);
-  const long NHW = dy.numel() / Cp;
-  auto dx = at::empty_like(dy);
-  hipLaunchKernelGGL(k_normalize_nhwc_bwd, dim3(grid1d(NHW)), dim3(TPB), 0,
-                     cur_stream(), (const bf16_t*)dy.contiguous().data_ptr(),
-                     (bf16_t*)dx.data_ptr(), NHW, (int)Cp);
-  HIP_CHECK_LAST();
-  return dx;
-}
-
-at::Tensor nchw_to_nhwc(const at::Tensor& x, int64_t Cp) {
-  TORCH_CHECK(x.is_cuda() && x.dtype() == at::kFloat && x.dim() == 4);
-  const long N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
-  auto y = at::empty({N, H, W, Cp}, x.options().dtype(at::kBFloat16));
-  const long NHW = N * H * W;
-  hipLaunchKernelGGL(k_nchw2nhwc,
-                     dim3((unsigned)((NHW + 255) / 256), 1, (unsigned)(Cp / 16)),
-                     dim3(256), 0,
-                     cur_stream(), x.contiguous().data_ptr<float>(),
-                     (bf16_t*)y.data_ptr(), NHW, H * W, (int)C, (int)Cp);
-  HIP_CHECK_LAST();
-  return y;
-}
-
-at::Tensor nhwc_to_nchw(const at::Tensor& x, int64_t C) {
-  TORCH_CHECK(x.is_cuda() && x.dtype() == at::kBFloat16 && x.dim() == 4);
-  const long N = x.size(0), H = x.size(1), W = x.size(2), Cp = x.size(3);
-  auto y = at::empty({N, C, H, W}, x.options().dtype(at::kFloat));
-  const long NHW = N * H * W;
-  hipLaunchKernelGGL(k_nhwc2nchw,
-                     dim3((unsigned)((NHW + 255) / 256), 1, (unsigned)(Cp / 16)),
-                     dim3(256), 0,
-                     cur_stream(), (const bf16_t*)x.contiguous().data_ptr(),
-                     y.data_ptr<float>(), NHW, H * W, (int)C, (int)Cp);
-  HIP_CHECK_LAST();
-  return y;
-}
-
-at::Tensor fusion_fwd(const at::Tensor& maps, const at::Tensor& rwb,
-                      const at::Tensor& rce, const at::Tensor& rgc) {
-  TORCH_CHECK(dense_bf16(maps) && dense_bf16(rwb) && dense_bf16(rce) &&
-                  dense_bf16(rgc),
-              "fusion_fwd: all tensors must be contiguous bf16 on the GPU");
-  TORCH_CHECK(maps.dim() == 4 && maps.size(3) == 16,
-              "fusion_fwd: maps must be (N,H,W,16)");
-  TORCH_CHECK(rwb.sizes() == maps.sizes() && rce.sizes() == maps.sizes() &&
-                  rgc.sizes() == maps.sizes() &&
-                  rwb.device() == maps.device() &&
-                  rce.device() == maps.device() &&
-                  rgc.device() == maps.device(),
-              "fusion_fwd: tensors differ in shape or device");
-  const long N = maps.size(0), H = maps.size(1), W = maps.size(2);
-  const long NHW = N * H * W;
-  auto out = at::empty_like(maps);
-  if (NHW == 0) return out;
-  hipLaunchKernelGGL(k_fusion_fwd, dim3(grid1d(NHW)), dim3(TPB), 0,
-                     cur_stream(), (const bf16_t*)maps.data_ptr(),
-                     (const bf16_t*)rwb.data_ptr(),
-                     (const bf16_t*)rce.data_ptr(),
-                     (const bf16_t*)rgc.data_ptr(), (bf16_t*)out.data_ptr(),
-                     NHW);
-  HIP_CHECK_LAST();
-  return out;
-}
-
-std::vector<at::Tensor> fusion_bwd(const at::Tensor& dout,
-                                   const at::Tensor& maps,
-                                   const at::Tensor& rwb,
-                                   const at::Tensor& rce,
-                                   const at::Tensor& rgc) {
-  TORCH_CHECK(dense_bf16(dout) && dense_bf16(maps) && dense_bf16(rwb) &&
-                  dense_bf16(rce) && dense_bf16(rgc),
-              "fusion_bwd: all tensors must be contiguous bf16 on the GPU");
-  TORCH_CHECK(maps.dim() == 4 && maps.size(3) == 16,
-              "fusion_bwd: maps must be (N,H,W,16)");
-  TORCH_CHECK(dout.sizes() == maps.sizes() && rwb.sizes() == maps.sizes() &&
-                  rce.sizes() == maps.sizes() &&
-                  rgc.sizes() == maps.sizes() &&
-                  dout.device() == maps.device() &&
-                  rwb.device() == maps.device() &&
-                  rce.device() == maps.device() &&
-                  rgc.device() == maps.device(),
-              "fusion_bwd: tensors differ in shape or device");
-  const long N = maps.size(0), H = maps.size(1), W = maps.size(2);
-  const long NHW = N * H * W;
-  auto dmaps = at::empty_like(maps);
-  auto drwb = at::empty_like(maps);
-  auto drce = at::empty_like(maps);
-  auto drgc = at::empty_like(maps);
-  if (NHW == 0) return {dmaps, drwb, drce, drgc};
-  hipLaunchKernelGGL(k_fusion_bwd, dim3(grid1d(NHW)), dim3(TPB), 0,
-                     cur_stream(), (const bf16_t*)dout.data_ptr(),
-                     (const bf16_t*)maps.data_ptr(),
-                     (const bf16_t*)rwb.data_ptr(),
-                     (const bf16_t*)rce.data_ptr(),
-                     (const bf16_t*)rgc.data_ptr(), (bf16_t*)dmaps.data_ptr(),
-                     (bf16_t*)drwb.data_ptr(), (bf16_t*)drce.data_ptr(),
-                     (bf16_t*)drgc.data_ptr(), NHW);
-  HIP_CHECK_LAST();
-  return {dmaps, drwb, drce, drgc};
-}
-
-at::Tensor act_bwd(const at::Tensor& dy, const at::Tensor& y, int64_t act) {
-  TORCH_CHECK(dense_bf16(dy) && dense_bf16(y),
-              "act_bwd: dy and y must be contiguous bf16 on the GPU");
-  TORCH_CHECK(y.sizes() == dy.sizes() && y.device() == dy.device(),
-              "act_bwd: dy and y differ in shape or device");
-  TORCH_CHECK(act == ACT_RELU || act == ACT_SIGMOID,
-              "act_bwd: act must be relu (1) or sigmoid (2)");
-  auto dpre = at::empty_like(dy);
-  const long n = dy.numel();
-  if (n == 0) return dpre;
-  hipLaunchKernelGGL(k_act_bwd, dim3(grid1d((n + 7) / 8)), dim3(TPB), 0,
-                     cur_stream(),
-                     (const bf16_t*)dy.data_ptr(),
-                     (const bf16_t*)y.data_ptr(), (bf16_t*)dpre.data_ptr(),
-                     n, (int)act);
-  HIP_CHECK_LAST();
-  return dpre;
-}
-
-at::Tensor normalize_vgg_fwd(const at::Tensor& x, int64_t Cp) {
-  const long N = x.size(0), H = x.size(2), W = x.size(3);
-  const long NHW = N * H * W;
-  auto y = at::empty({N, H, W, Cp}, x.options().dtype(at::kBFloat16));
-  hipLaunchKernelGGL(k_normalize_vgg_fwd, dim3(grid1d(NHW)), dim3(TPB), 0,
-                     cur_stream(), x.contiguous().data_ptr<float>(),
-                     (bf16_t*)y.data_ptr(), NHW, H * W, (int)Cp);
-  HIP_CHECK_LAST();
-  return y;
-}
-
-at::Tensor normalize_vgg_bwd(const at::Tensor& dy, int64_t C) {
-  TORCH_CHECK(C == 3);
-  const long N = dy.size(0), H = dy.size(1), W = dy.size(2),
-             Cp = dy.size(3);
-  auto dx = at::empty({N, C, H, W}, dy.options().dtype(at::kFloat));
-  const long NHW = N * H * W;
-  hipLaunchKernelGGL(k_normalize_vgg_bwd, dim3(grid1d(NHW)), dim3(TPB), 0,
-                     cur_stream(), (const bf16_t*)dy.contiguous().data_ptr(),
-                     dx.data_ptr<float>(), NHW, H * W, (int)Cp);
-  HIP_CHECK_LAST();
-  return dx;
-}
-
 at::Tensor sqdiff255_sum(const at::Tensor& a, const at::Tensor& b,
                          int64_t Clog) {
-  TORCH_CHECK(a.sizes() == b.sizes());
+  TORCH_CHECK(dense(a, at::kBFloat16, 4) && dense_like(b, a),
+              "sqdiff255_sum: a and b must be contiguous (N,H,W,Cp) bf16 on "
+              "the GPU, of one shape and device");
+  const long Cp = a.size(3), n = a.numel();
+  TORCH_CHECK(logical_channels(Clog, Cp),
+              "sqdiff255_sum: Clog must be in [1, Cp]");
   auto out = at::zeros({}, a.options().dtype(at::kDouble));
-  const long Cp = a.size(3);
-  if (Clog == Cp) {
-    const long n = a.numel();
-    hipLaunchKernelGGL(k_sqdiff255_flat,
-                       dim3(grid1d((n + 7) / 8, TPB, SQD_MAX_BLOCKS)),
-                       dim3(TPB), 0,
-                       cur_stream(), (const bf16_t*)a.data_ptr(),
-                       (const bf16_t*)b.data_ptr(), out.data_ptr<double>(),
-                       n);
-  } else {
-    const long NHW = a.numel() / Cp;
-    hipLaunchKernelGGL(k_sqdiff255_pix,
-                       dim3(grid1d(NHW, TPB, SQD_MAX_BLOCKS)), dim3(TPB), 0,
-                       cur_stream(), (const bf16_t*)a.data_ptr(),
-                       (const bf16_t*)b.data_ptr(), out.data_ptr<double>(),
-                       NHW, (int)Clog, (int)Cp);
-  }
-  HIP_CHECK_LAST();
+  if (Clog == Cp)
+    launch1d_capped(k_sqdiff255_flat, (n + 7) / 8, SQD_MAX_BLOCKS, cbf(a),
+                    cbf(b), out.data_ptr<double>(), n);
+  else
+    launch1d_capped(k_sqdiff255_pix, n / Cp, SQD_MAX_BLOCKS, cbf(a), cbf(b),
+                    out.data_ptr<double>(), n / Cp, (int)Clog, (int)Cp);
   return out;
 }
 
 at::Tensor sqdiff255_bwd(const at::Tensor& a, const at::Tensor& b,
                          const at::Tensor& gscale, double sign) {
-  TORCH_CHECK(dense_bf16(a) && dense_bf16(b),
-              "sqdiff255_bwd: a and b must be contiguous bf16 on the GPU");
-  TORCH_CHECK(b.sizes() == a.sizes() && b.device() == a.device(),
-              "sqdiff255_bwd: a and b differ in shape or device");
-  TORCH_CHECK(gscale.is_cuda() && gscale.dtype() == at::kFloat &&
-                  gscale.numel() == 1 && gscale.device() == a.device(),
+  TORCH_CHECK(dense(a, at::kBFloat16) && dense_like(b, a),
+              "sqdiff255_bwd: a and b must be contiguous bf16 on the GPU, of "
+              "one shape and device");
+  TORCH_CHECK(device_scalar(gscale, at::kFloat, a) && gscale.numel() == 1,
               "sqdiff255_bwd: gscale must be one fp32 value on a's device");
   auto da = at::empty_like(a);
   const long n = a.numel();
-  if (n == 0) return da;
-  hipLaunchKernelGGL(k_sqdiff255_bwd, dim3(grid1d(n)), dim3(TPB), 0,
-                     cur_stream(), (const bf16_t*)a.data_ptr(),
-                     (const bf16_t*)b.data_ptr(), gscale.data_ptr<float>(),
-                     (bf16_t*)da.data_ptr(), n, (float)sign);
-  HIP_CHECK_LAST();
+  launch1d(k_sqdiff255_bwd, n, cbf(a), cbf(b), gscale.data_ptr<float>(),
+           bf(da), n, (float)sign);
   return da;
-}
-
-at::Tensor out_to_u8(const at::Tensor& x) {
-  TORCH_CHECK(x.is_cuda() && x.dtype() == at::kBFloat16 && x.dim() == 4);
-  const long N = x.size(0), H = x.size(1), W = x.size(2), Cp = x.size(3);
-  auto y = at::empty({N, H, W, 3}, x.options().dtype(at::kByte));
-  const long NHW = N * H * W;
-  hipLaunchKernelGGL(k_out_to_u8, dim3(grid1d(NHW)), dim3(TPB), 0,
-                     cur_stream(), (const bf16_t*)x.contiguous().data_ptr(),
-                     y.data_ptr<uint8_t>(), NHW, (int)Cp);
-  HIP_CHECK_LAST();
-  return y;
-}
-
-at::Tensor u8_to_nchw(const at::Tensor& x) {
-  TORCH_CHECK(x.is_cuda() && x.dtype() == at::kByte && x.dim() == 4 &&
-              x.size(3) == 3);
-  const long N = x.size(0), H = x.size(1), W = x.size(2);
-  auto y = at::empty({N, 3, H, W}, x.options().dtype(at::kFloat));
-  const long NHW = N * H * W;
-  hipLaunchKernelGGL(k_u8_to_nchw, dim3(grid1d(NHW)), dim3(TPB), 0,
-                     cur_stream(), x.contiguous().data_ptr<uint8_t>(),
-                     y.data_ptr<float>(), NHW, H * W);
-  HIP_CHECK_LAST();
-  return y;
 }
 
 void adam_step(at::Tensor& p, const at::Tensor& g, at::Tensor& m,
                at::Tensor& v, const at::Tensor& lr_buf, double b1, double b2,
                double eps, at::Tensor& step_buf) {
-  TORCH_CHECK(p.is_cuda() && p.dtype() == at::kFloat);
-  TORCH_CHECK(lr_buf.dtype() == at::kFloat && step_buf.dtype() == at::kInt);
+  TORCH_CHECK(dense(p, at::kFloat),
+              "adam_step: p must be contiguous fp32 on the GPU");
+  TORCH_CHECK(dense_like(g, p) && dense_like(m, p) && dense_like(v, p),
+              "adam_step: g, m and v must be contiguous, of p's dtype, shape "
+              "and device");
+  TORCH_CHECK(device_scalar(lr_buf, at::kFloat, p) &&
+                  device_scalar(step_buf, at::kInt, p),
+              "adam_step: lr_buf (fp32) and step_buf (int32) must hold a "
+              "value on p's device");
   const long n = p.numel();
+  if (n == 0) return;
   hipLaunchKernelGGL(k_adam_tick, dim3(1), dim3(64), 0, cur_stream(),
                      step_buf.data_ptr<int>());
-  hipLaunchKernelGGL(k_adam, dim3(grid1d(n)), dim3(TPB), 0, cur_stream(),
-                     p.data_ptr<float>(), g.data_ptr<float>(),
-                     m.data_ptr<float>(), v.data_ptr<float>(), n,
-                     lr_buf.data_ptr<float>(), (float)b1, (float)b2,
-                     (float)eps, step_buf.data_ptr<int>());
-  HIP_CHECK_LAST();
+  launch1d(k_adam, n, p.data_ptr<float>(), g.data_ptr<float>(),
+           m.data_ptr<float>(), v.data_ptr<float>(), n,
+           lr_buf.data_ptr<float>(), (float)b1, (float)b2, (float)eps,
+           step_buf.data_ptr<int>());
 }
 
 // ---------------------------------------------------------------------------
@@ -934,39 +925,22 @@ void gather_augment_u8(const at::Tensor& cache_raw,
                        const at::Tensor& cache_ref, const at::Tensor& idx,
                        const at::Tensor& codes, at::Tensor& out_raw,
                        at::Tensor& out_ref, bool allow_transpose) {
-  TORCH_CHECK(cache_raw.is_cuda() && cache_ref.is_cuda() && idx.is_cuda() &&
-                  codes.is_cuda() && out_raw.is_cuda() && out_ref.is_cuda(),
-              "gather_augment_u8: all tensors must be on the GPU");
-  const auto dev = cache_raw.device();
-  TORCH_CHECK(cache_ref.device() == dev && idx.device() == dev &&
-                  codes.device() == dev && out_raw.device() == dev &&
-                  out_ref.device() == dev,
-              "gather_augment_u8: all tensors must be on the same device");
-  TORCH_CHECK(cache_raw.dtype() == at::kByte &&
-                  cache_ref.dtype() == at::kByte &&
-                  out_raw.dtype() == at::kByte && out_ref.dtype() == at::kByte,
-              "gather_augment_u8: caches and outputs must be uint8");
-  TORCH_CHECK(idx.dtype() == at::kInt && codes.dtype() == at::kInt,
-              "gather_augment_u8: idx and codes must be int32");
-  TORCH_CHECK(cache_raw.dim() == 4 && cache_raw.size(3) == 3 &&
-                  cache_raw.size(0) >= 1,
-              "gather_augment_u8: cache must be (Nc>=1, H, W, 3)");
-  TORCH_CHECK(cache_ref.sizes() == cache_raw.sizes(),
-              "gather_augment_u8: cache_raw / cache_ref shapes differ");
-  TORCH_CHECK(idx.dim() == 1 && codes.dim() == 1 &&
-                  idx.size(0) == codes.size(0),
-              "gather_augment_u8: idx and codes must both be (B,)");
+  TORCH_CHECK(dense(cache_raw, at::kByte, 4) && cache_raw.size(3) == 3 &&
+                  cache_raw.size(0) >= 1 && dense_like(cache_ref, cache_raw),
+              "gather_augment_u8: the caches must be contiguous (Nc>=1,H,W,3) "
+              "uint8 on the GPU, of one shape and device");
+  TORCH_CHECK(dense(idx, at::kInt, 1) && dense_like(codes, idx) &&
+                  idx.device() == cache_raw.device(),
+              "gather_augment_u8: idx and codes must both be contiguous (B,) "
+              "int32 on the caches' device");
   const long Nc = cache_raw.size(0), H = cache_raw.size(1),
              W = cache_raw.size(2), B = idx.size(0);
-  TORCH_CHECK(out_raw.dim() == 4 && out_raw.size(0) == B &&
-                  out_raw.size(1) == H && out_raw.size(2) == W &&
-                  out_raw.size(3) == 3 && out_ref.sizes() == out_raw.sizes(),
-              "gather_augment_u8: outputs must be (B, H, W, 3) matching "
-              "the cache and idx");
-  TORCH_CHECK(cache_raw.is_contiguous() && cache_ref.is_contiguous() &&
-                  idx.is_contiguous() && codes.is_contiguous() &&
-                  out_raw.is_contiguous() && out_ref.is_contiguous(),
-              "gather_augment_u8: all tensors must be contiguous");
+  TORCH_CHECK(dense(out_raw, at::kByte, 4) &&
+                  out_raw.sizes() == at::IntArrayRef({B, H, W, 3}) &&
+                  out_raw.device() == cache_raw.device() &&
+                  dense_like(out_ref, out_raw),
+              "gather_augment_u8: the outputs must be contiguous (B,H,W,3) "
+              "uint8 matching the caches and idx, on their device");
   TORCH_CHECK(H % 8 == 0 && W % 8 == 0,
               "gather_augment_u8: H and W must be divisible by 8");
   TORCH_CHECK(!allow_transpose || H == W,

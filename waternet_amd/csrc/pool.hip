@@ -5,10 +5,7 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "common.h"
-
-namespace {
-inline hipStream_t cur_stream() { return at::cuda::getCurrentHIPStream(); }
-}
+#include "host_check.h"
 
 __global__ void k_maxpool_fwd(const bf16_t* __restrict__ x,
                               bf16_t* __restrict__ y,
@@ -58,8 +55,7 @@ __global__ void k_maxpool_bwd(const bf16_t* __restrict__ dy,
 }
 
 std::vector<at::Tensor> maxpool2x2_fwd(const at::Tensor& x) {
-  TORCH_CHECK(x.is_cuda() && x.dtype() == at::kBFloat16 && x.dim() == 4 &&
-                  x.is_contiguous(),
+  TORCH_CHECK(dense(x, at::kBFloat16, 4),
               "maxpool2x2_fwd: x must be contiguous (N,H,W,Cp) bf16 on the "
               "GPU");
   const long N = x.size(0), H = x.size(1), W = x.size(2), Cp = x.size(3);
@@ -67,24 +63,18 @@ std::vector<at::Tensor> maxpool2x2_fwd(const at::Tensor& x) {
   auto y = at::empty({N, OH, OW, Cp}, x.options());
   auto idx = at::empty({N, OH, OW, Cp}, x.options().dtype(at::kByte));
   const long NOHW = N * OH * OW;
-  if (NOHW * Cp == 0) return {y, idx};
-  const int blocks = (int)std::min<long>(4096, (NOHW * Cp + 255) / 256);
-  hipLaunchKernelGGL(k_maxpool_fwd, dim3(blocks), dim3(256), 0, cur_stream(),
-                     (const bf16_t*)x.data_ptr(), (bf16_t*)y.data_ptr(),
-                     idx.data_ptr<uint8_t>(), NOHW, (int)OH, (int)OW, (int)H,
-                     (int)W, (int)Cp);
-  HIP_CHECK_LAST();
+  launch1d(k_maxpool_fwd, NOHW * Cp, (const bf16_t*)x.data_ptr(),
+           (bf16_t*)y.data_ptr(), idx.data_ptr<uint8_t>(), NOHW, (int)OH,
+           (int)OW, (int)H, (int)W, (int)Cp);
   return {y, idx};
 }
 
 at::Tensor maxpool2x2_bwd(const at::Tensor& dy, const at::Tensor& idx,
                           int64_t H, int64_t W) {
-  TORCH_CHECK(dy.is_cuda() && dy.dtype() == at::kBFloat16 && dy.dim() == 4 &&
-                  dy.is_contiguous(),
+  TORCH_CHECK(dense(dy, at::kBFloat16, 4),
               "maxpool2x2_bwd: dy must be contiguous (N,OH,OW,Cp) bf16 on "
               "the GPU");
-  TORCH_CHECK(idx.is_cuda() && idx.dtype() == at::kByte &&
-                  idx.is_contiguous() && idx.sizes() == dy.sizes() &&
+  TORCH_CHECK(dense(idx, at::kByte) && idx.sizes() == dy.sizes() &&
                   idx.device() == dy.device(),
               "maxpool2x2_bwd: idx must be contiguous uint8 of dy's shape on "
               "dy's device");
@@ -94,12 +84,8 @@ at::Tensor maxpool2x2_bwd(const at::Tensor& dy, const at::Tensor& idx,
               "maxpool2x2_bwd: (H, W) does not pool to dy's (OH, OW)");
   auto dx = at::zeros({N, H, W, Cp}, dy.options());
   const long NOHW = N * OH * OW;
-  if (NOHW * Cp == 0) return dx;
-  const int blocks = (int)std::min<long>(4096, (NOHW * Cp + 255) / 256);
-  hipLaunchKernelGGL(k_maxpool_bwd, dim3(blocks), dim3(256), 0, cur_stream(),
-                     (const bf16_t*)dy.data_ptr(), idx.data_ptr<uint8_t>(),
-                     (bf16_t*)dx.data_ptr(), NOHW, (int)OH, (int)OW, (int)H,
-                     (int)W, (int)Cp);
-  HIP_CHECK_LAST();
+  launch1d(k_maxpool_bwd, NOHW * Cp, (const bf16_t*)dy.data_ptr(),
+           idx.data_ptr<uint8_t>(), (bf16_t*)dx.data_ptr(), NOHW, (int)OH,
+           (int)OW, (int)H, (int)W, (int)Cp);
   return dx;
 }

@@ -19,10 +19,7 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "common.h"
-
-namespace {
-inline hipStream_t cur_stream() { return at::cuda::getCurrentHIPStream(); }
-}
+#include "host_check.h"
 
 // ---------------------------------------------------------------------------
 // Histograms (RGB channels, whole image) for white balance
@@ -193,12 +190,8 @@ at::Tensor rgb2lab_u8(const at::Tensor& rgb_u8) {
   auto rgb = rgb_u8.contiguous();
   auto lab = at::empty_like(rgb);
   const long total = rgb.numel() / 3;
-  if (total == 0) return lab;
-  hipLaunchKernelGGL(k_rgb2lab,
-                     dim3(std::min<long>(4096, (total + 255) / 256)),
-                     dim3(256), 0, cur_stream(), rgb.data_ptr<uint8_t>(),
-                     lab.data_ptr<uint8_t>(), total);
-  HIP_CHECK_LAST();
+  launch1d(k_rgb2lab, total, rgb.data_ptr<uint8_t>(),
+           lab.data_ptr<uint8_t>(), total);
   return lab;
 }
 
@@ -364,14 +357,13 @@ std::vector<at::Tensor> preprocess_all(const at::Tensor& raw_u8) {
                      (const unsigned int*)hist.data_ptr<int>(),
                      params.data_ptr<float>(), HW);
   hipLaunchKernelGGL(k_wb_gc_apply,
-                     dim3(std::min<long>(1024, (HW + 255) / 256), N),
+                     dim3(grid1d(HW, TPB, 1024), N),
                      dim3(256), 0, stream, raw.data_ptr<uint8_t>(),
                      params.data_ptr<float>(), glut.data_ptr<uint8_t>(),
                      wb.data_ptr<uint8_t>(), gc.data_ptr<uint8_t>(), HW);
   const long total = (long)N * HW;
   hipLaunchKernelGGL(k_rgb2lab,
-                     dim3(std::min<long>(4096, (total + 255) / 256)),
-                     dim3(256), 0, stream, raw.data_ptr<uint8_t>(),
+                     dim3(grid1d(total)), dim3(256), 0, stream, raw.data_ptr<uint8_t>(),
                      lab.data_ptr<uint8_t>(), total);
   hipLaunchKernelGGL(k_clahe_hist, dim3(N, 64), dim3(256), 0, stream,
                      lab.data_ptr<uint8_t>(),
@@ -382,7 +374,7 @@ std::vector<at::Tensor> preprocess_all(const at::Tensor& raw_u8) {
                      (unsigned int*)thists.data_ptr<int>(),
                      luts.data_ptr<uint8_t>(), tileArea, clip);
   hipLaunchKernelGGL(k_clahe_interp_lab2rgb,
-                     dim3(std::min<long>(1024, (HW + 255) / 256), N),
+                     dim3(grid1d(HW, TPB, 1024), N),
                      dim3(256), 0, stream, lab.data_ptr<uint8_t>(),
                      luts.data_ptr<uint8_t>(), he.data_ptr<uint8_t>(), H, W);
   HIP_CHECK_LAST();

@@ -61,8 +61,10 @@ def structural_similarity_index_measure(
 
 def _ssim_torch(preds, target, data_range, kernel_size=11, sigma=1.5,
                 k1=0.01, k2=0.03):
-    preds = preds.float()
-    target = target.float()
+    # fp32 unless the caller brings float64 (the tests' reference precision)
+    dtype = torch.float64 if preds.dtype == torch.float64 else torch.float32
+    preds = preds.to(dtype)
+    target = target.to(dtype)
     n, c, h, w = preds.shape
     kern = _gaussian_kernel2d(kernel_size, sigma, preds.device, preds.dtype)
     kern = kern.expand(c, 1, kernel_size, kernel_size).contiguous()
