@@ -26,6 +26,10 @@ Extensions (do not break reference invocations):
   --device-cache   fast engine: decode/resize the dataset once, keep the
                    uint8 pairs on the GPU and gather + augment each
                    minibatch there (waternet_amd.data.device_cache)
+  --ssim-weight W  add W * (1 - SSIM) to the training loss (default 0 = the
+                   reference loss). W is in the unit of the 255-scale MSE;
+                   the fast engine differentiates SSIM with its HIP
+                   kernels, the eager engine with torch autograd
 
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N
 train.py ...` — one rank per GPU, RCCL all-reduce gradient sync
@@ -96,6 +100,11 @@ def parse_args(argv=None):
                              "once, keep the uint8 pairs on the GPU and "
                              "gather + augment each minibatch with one HIP "
                              "kernel instead of the DataLoaders")
+    parser.add_argument("--ssim-weight", type=float, default=0.0,
+                        metavar="W",
+                        help="add W * (1 - SSIM) to the training loss "
+                             "0.05*perceptual + mse255 (same unit as "
+                             "mse255); 0 = reference loss")
     return parser.parse_args(argv)
 
 
@@ -220,6 +229,8 @@ def _eval_epoch_fast(engine, loader, device):
 def main(argv=None):
     start_ts = timer()
     args = parse_args(argv)
+    if not args.ssim_weight >= 0:
+        raise SystemExit("--ssim-weight must be >= 0")
 
     dist_env = init_distributed()
     rank0 = dist_env.rank == 0
@@ -346,6 +357,7 @@ def main(argv=None):
             # keep the RCCL collective out of graph capture under DDP
             # (same policy as bench.py)
             use_graph=(not args.no_graph) and dist_env.world_size == 1,
+            ssim_weight=args.ssim_weight,
         )
         optimizer, scheduler = engine.opt, engine.sched
         vgg_model = engine.vgg
@@ -420,6 +432,7 @@ def main(argv=None):
                 model, train_loader, optimizer, scheduler, vgg_model, device,
                 epoch_num=epoch, total_epochs=args.epochs,
                 grad_reducer=reducer, progress=rank0,
+                ssim_weight=args.ssim_weight,
             )
             val_metrics = eval_one_epoch(model, val_loader, device, vgg_model)
 
@@ -483,6 +496,8 @@ def main(argv=None):
         }
         if args.device_cache:
             config["device_cache"] = True
+        if args.ssim_weight:
+            config["ssim_weight"] = args.ssim_weight
         with open(savedir / "config.json", "w") as f:
             json.dump(config, f, indent=4)
         print(f"Metrics and weights saved to {savedir}")

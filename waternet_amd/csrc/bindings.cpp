@@ -74,6 +74,13 @@ at::Tensor ssim_sum(const at::Tensor& a, const at::Tensor& b,
 at::Tensor ssim_sum_nhwc(const at::Tensor& a, const at::Tensor& b,
                          int64_t Clog, double data_range, double k1,
                          double k2);
+std::vector<at::Tensor> ssim_fwd_save_nhwc(const at::Tensor& a,
+                                           const at::Tensor& b, int64_t Clog,
+                                           double data_range, double k1,
+                                           double k2);
+at::Tensor ssim_bwd_nhwc(const at::Tensor& a, const at::Tensor& b,
+                         const at::Tensor& dmaps, const at::Tensor& gscale,
+                         int64_t Clog);
 
 // preprocess.hip
 std::vector<at::Tensor> preprocess_all(const at::Tensor& raw_u8);
@@ -128,6 +135,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("maxpool2x2_bwd", &maxpool2x2_bwd);
   m.def("ssim_sum", &ssim_sum);
   m.def("ssim_sum_nhwc", &ssim_sum_nhwc);
+  m.def("ssim_fwd_save_nhwc", &ssim_fwd_save_nhwc,
+        "ssim_sum_nhwc + the (N,Clog,3,OH,OW) fp32 derivative maps");
+  m.def("ssim_bwd_nhwc", &ssim_bwd_nhwc,
+        "d(mean SSIM)/da from the saved maps, (N,H,W,Cp) bf16");
   m.def("preprocess_all", &preprocess_all);
   m.def("rgb2lab_u8", &rgb2lab_u8,
         "uint8 NHW3 RGB -> uint8 NHW3 LAB (OpenCV 8-bit scaling)");

@@ -10,6 +10,10 @@ Per step (reference per-minibatch work):
   all-reduce overlapped with metrics] -> fused Adam + per-minibatch StepLR
   -> SSIM/PSNR metrics accumulated on-device.
 
+ssim_weight > 0 (opt-in, beyond the reference) adds ssim_weight * (1 - SSIM)
+to the loss through the HIP SSIM backward; the step's SSIM metric is then
+the value of that same forward.
+
 hipGraph capture (use_graph=True): the whole step (preprocess through Adam
 and metric accumulation) is captured once and replayed per step, removing
 ~150 host launch overheads; fresh data is copied into the static input
@@ -35,7 +39,7 @@ from waternet_amd.ops.adam import FusedAdam
 from waternet_amd.ops.functional import NormalizeNhwc, mse255_nhwc
 from waternet_amd.ops.preprocess import gpu_transform_batch
 from waternet_amd.utils.streams import DEBUG as STREAM_DEBUG, StreamJoin
-from waternet_amd.ops.ssim import ssim_nhwc
+from waternet_amd.ops.ssim import ssim_loss_nhwc, ssim_nhwc
 
 TRAIN_KEYS = ["loss", "perceptual", "mse255", "ssim", "psnr"]
 VAL_KEYS = ["mse", "ssim", "psnr", "perceptual_loss"]
@@ -80,7 +84,11 @@ class FastStepEngine:
 
     def __init__(self, model, batch_size=16, height=112, width=112,
                  device="cuda:0", world_size=1, use_graph=True, lr=1e-3,
-                 vgg_seed=VGG_SEED):
+                 vgg_seed=VGG_SEED, ssim_weight=0.0):
+        """ssim_weight: weight W of the opt-in loss term W * (1 - SSIM),
+        in the unit of mse255 (which spans 0..255^2 while 1 - SSIM spans
+        0..2, so W is the mse255 the term is worth at SSIM 0); 0 keeps
+        the reference loss 0.05 * perceptual + mse255."""
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("FastStepEngine requires a ROCm GPU "
@@ -90,6 +98,9 @@ class FastStepEngine:
             raise RuntimeError(
                 "FastStepEngine requires the native HIP extension: "
                 f"{native_load_error()}")
+        if not ssim_weight >= 0:
+            raise ValueError(f"ssim_weight must be >= 0, got {ssim_weight}")
+        self.ssim_weight = float(ssim_weight)
         self.world = world_size
         self.bs = batch_size
         self.h, self.w = height, width
@@ -190,6 +201,13 @@ class FastStepEngine:
             perceptual = mse255_nhwc(fx, fy, 512)
             mse = mse255_nhwc(out_nhwc, ref_nhwc, 3)
             loss = PERCEPTUAL_WEIGHT * perceptual + mse
+            ssim = None
+            if self.ssim_weight > 0:
+                # one SSIM forward per step: the loss term's value is also
+                # the metric (as PSNR reuses the MSE reduction)
+                ssim = ssim_loss_nhwc(out_nhwc, ref_nhwc, 3, 1.0)
+                loss = loss + self.ssim_weight * (1.0 - ssim)
+                ssim = ssim.detach()
 
         with trace_range("backward"):
             self.opt.zero_grad()
@@ -209,8 +227,8 @@ class FastStepEngine:
                 comm_join.mark()
 
         with trace_range("metrics"), torch.no_grad():
-            out_d = out_nhwc.detach()
-            ssim = ssim_nhwc(out_d, ref_nhwc, 3, 1.0)
+            if ssim is None:
+                ssim = ssim_nhwc(out_nhwc.detach(), ref_nhwc, 3, 1.0)
             mse01 = mse.detach().double() / (255.0 * 255.0)
             psnr = 10.0 * torch.log10(1.0 / mse01)
             self.metric_sums += torch.stack([
@@ -360,12 +378,13 @@ class BenchTrainer(FastStepEngine):
 
     def __init__(self, batch_size=16, height=112, width=112, device="cuda:0",
                  world_size=1, seed=0, use_graph=True, pool_size=4,
-                 lr=1e-3):
+                 lr=1e-3, ssim_weight=0.0):
         torch.manual_seed(seed)
         model = WaterNet().to(torch.device(device))
         super().__init__(model, batch_size=batch_size, height=height,
                          width=width, device=device, world_size=world_size,
-                         use_graph=use_graph, lr=lr)
+                         use_graph=use_graph, lr=lr,
+                         ssim_weight=ssim_weight)
         # synthetic uint8 data pool (deterministic per rank), kept in PINNED
         # HOST memory. The images are spatially-correlated noise (low-res
         # noise bilinearly upsampled + fine noise), matching natural-image

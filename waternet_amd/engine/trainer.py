@@ -38,9 +38,11 @@ def train_one_epoch(
     total_epochs=1,
     grad_reducer=None,
     progress=True,
+    ssim_weight=0.0,
 ):
     """One epoch of training. grad_reducer: optional callable invoked after
-    backward and before optimizer.step() (DDP flat-bucket all-reduce)."""
+    backward and before optimizer.step() (DDP flat-bucket all-reduce).
+    ssim_weight: weight of the opt-in (1 - SSIM) loss term (composite_loss)."""
     model.train()
     epoch_metrics = {k: 0.0 for k in TRAIN_METRICS_NAMES}
     n_batches = len(train_dataloader)
@@ -66,7 +68,8 @@ def train_one_epoch(
         # the reference call (train.py:108 -> net.py:99).
         out = model(batch["raw"], batch["wb"], batch["he"], batch["gc"])
 
-        loss, ploss, mloss = composite_loss(out, batch["ref"], vgg_model)
+        loss, ploss, mloss = composite_loss(out, batch["ref"], vgg_model,
+                                            ssim_weight)
 
         optimizer.zero_grad(set_to_none=True)
         loss.backward()
