@@ -43,7 +43,27 @@ def parse_args(argv=None):
                         help="print no-reference UIQM/UCIQE before and "
                              "after per source and append them to "
                              "<savedir>/quality.csv")
-    return parser.parse_args(argv)
+    parser.add_argument("--temporal-smooth", type=float, default=None,
+                        metavar="A",
+                        help="video sources only: smooth the white-balance "
+                             "clip points and CLAHE tile LUTs over the "
+                             "frames with weight A in (0,1] on the new "
+                             "frame (1 = per-frame statistics, smaller = "
+                             "steadier); default off. Images stay "
+                             "independent.")
+    parser.add_argument("--scene-cut", type=float, default=0.5, metavar="T",
+                        help="with --temporal-smooth: restart the smoothing "
+                             "when the luminance histogram changes by more "
+                             "than the fraction T in [0,1] of its largest "
+                             "possible change. The default 0.5 is untuned "
+                             "on real footage.")
+    args = parser.parse_args(argv)
+    a = args.temporal_smooth
+    if a is not None and not 0.0 < a <= 1.0:  # also false for nan
+        parser.error(f"--temporal-smooth must be in (0,1], got {a}")
+    if not 0.0 <= args.scene_cut <= 1.0:
+        parser.error(f"--scene-cut must be in [0,1], got {args.scene_cut}")
+    return args
 
 
 def make_savedir(name):
@@ -96,15 +116,49 @@ def load_model(weights, device):
 _ENGINES = {}
 
 
-def _gpu_engine(model, h, w, device):
-    key = (id(model), h, w)
+def _gpu_engine(model, h, w, device, temporal=None):
+    key = (id(model), h, w) if temporal is None else \
+        (id(model), h, w, temporal.alpha, temporal.scene_cut)
     eng = _ENGINES.get(key)
     if eng is None:
         from waternet_amd.engine.inferencer import InferenceEngine
 
-        eng = InferenceEngine(model, h, w, device=device)
+        kw = {} if temporal is None else dict(
+            temporal_alpha=temporal.alpha, scene_cut=temporal.scene_cut)
+        eng = InferenceEngine(model, h, w, device=device, **kw)
         _ENGINES[key] = eng
     return eng
+
+
+class VideoTemporal:
+    """--temporal-smooth state of ONE video: which path carries the
+    smoothed statistics (the GPU engine's device state or the CPU
+    TemporalStabilizer) and its scene-cut count. A new one per video is
+    what resets the state: engines are cached across videos."""
+
+    def __init__(self, alpha, scene_cut):
+        self.alpha, self.scene_cut = alpha, scene_cut
+        self._engine = None
+        self._cpu = None
+
+    def engine(self, model, h, w, device):
+        eng = _gpu_engine(model, h, w, device, self)
+        if eng is not self._engine:  # first frame of this video
+            eng.reset_temporal()
+            self._engine = eng
+        return eng
+
+    def cpu_transform(self, rgb):
+        if self._cpu is None:
+            from waternet_amd.data.temporal import TemporalStabilizer
+
+            self._cpu = TemporalStabilizer(self.alpha, self.scene_cut)
+        return self._cpu.transform(rgb)
+
+    def cuts(self):
+        if self._engine is not None:
+            return self._engine.temporal_counters()["cuts"]
+        return self._cpu.cuts if self._cpu is not None else 0
 
 
 QUALITY_HEADER = ("source,frames,uiqm_before,uiqm_after,uciqe_before,"
@@ -154,12 +208,14 @@ class QualityReport:
 
 @torch.no_grad()
 def enhance_frame(model, rgb: np.ndarray, device,
-                  quality=None) -> np.ndarray:
+                  quality=None, temporal=None) -> np.ndarray:
     """uint8 HWC RGB -> enhanced uint8 HWC RGB. On GPU the whole frame
     pipeline (preprocess + forward + postprocess) runs as a hipGraph-
     captured on-device pipeline; on CPU the reference-semantics numpy
     transforms + eager model run. A QualityReport, when given, is fed the
-    frame's before/after no-reference metrics."""
+    frame's before/after no-reference metrics. A VideoTemporal, when given,
+    makes the frame the next one of its video: the WB/CLAHE statistics are
+    smoothed over the frames instead of taken from this frame alone."""
     if device.type == "cuda":
         from waternet_amd.ops import native_available
 
@@ -167,13 +223,18 @@ def enhance_frame(model, rgb: np.ndarray, device,
             from waternet_amd.engine.inferencer import pad8
 
             padded, h, w = pad8(rgb)
-            eng = _gpu_engine(model, padded.shape[0], padded.shape[1],
-                              device)
+            if temporal is None:
+                eng = _gpu_engine(model, padded.shape[0], padded.shape[1],
+                                  device)
+            else:
+                eng = temporal.engine(model, padded.shape[0],
+                                      padded.shape[1], device)
             out = eng.infer_frame(padded)[:h, :w]
             if quality is not None:
                 quality.add(eng.frame_quality(h, w))
             return out
-    wb, gc, he = transform(rgb)
+    wb, gc, he = transform(rgb) if temporal is None \
+        else temporal.cpu_transform(rgb)
     rgb_ten = arr2ten(rgb, add_batch_dim=True).to(device)
     wb_ten = arr2ten(wb, add_batch_dim=True).to(device)
     gc_ten = arr2ten(gc, add_batch_dim=True).to(device)
@@ -217,23 +278,27 @@ def run_image(model, path: Path, savedir: Path, device, show_split,
 
 
 def run_video(model, path: Path, savedir: Path, device, show_split,
-              report_quality=False):
+              report_quality=False, temporal_smooth=None, scene_cut=0.5):
     from waternet_amd.engine.video import FFmpegReader, FFmpegWriter
 
     quality = QualityReport() if report_quality else None
+    temporal = None if temporal_smooth is None \
+        else VideoTemporal(temporal_smooth, scene_cut)
     reader = FFmpegReader(path)
     savedir.mkdir(parents=True, exist_ok=True)  # late, ref inference.py:198
     outpath = savedir / path.name
     writer = FFmpegWriter(outpath, reader.width, reader.height, reader.fps)
     n = 0
     for frame in reader:
-        out = enhance_frame(model, frame, device, quality)
+        out = enhance_frame(model, frame, device, quality, temporal)
         writer.write(compose_split(frame, out) if show_split else out)
         n += 1
         if n % 50 == 0:
             print(f"{n} frames processed")
     writer.close()
     print(f"Wrote {n} frames to {outpath}")
+    if temporal is not None:
+        print(f"Scene cuts: {temporal.cuts()}")
     if quality is not None:
         quality.finish(path.name, savedir)
 
@@ -263,7 +328,8 @@ def main(argv=None):
     for p in sources:
         if p.suffix.lower() in VID_SUFFIXES:
             run_video(model, p, savedir, device, args.show_split,
-                      args.report_quality)
+                      args.report_quality, args.temporal_smooth,
+                      args.scene_cut)
         elif p.suffix.lower() in IM_SUFFIXES:
             run_image(model, p, savedir, device, args.show_split,
                       args.report_quality)

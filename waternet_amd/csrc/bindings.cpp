@@ -84,6 +84,16 @@ at::Tensor ssim_bwd_nhwc(const at::Tensor& a, const at::Tensor& b,
 
 // preprocess.hip
 std::vector<at::Tensor> preprocess_all(const at::Tensor& raw_u8);
+std::vector<at::Tensor> preprocess_stats(const at::Tensor& raw_u8);
+std::vector<at::Tensor> preprocess_apply(const at::Tensor& raw_u8,
+                                         const at::Tensor& lab,
+                                         const at::Tensor& wb_params,
+                                         const at::Tensor& luts);
+void temporal_blend(at::Tensor& wb, at::Tensor& lut, at::Tensor& lhist,
+                    at::Tensor& counters, at::Tensor& lut_u8,
+                    const at::Tensor& wb_params, const at::Tensor& luts,
+                    const at::Tensor& tile_hists, double alpha,
+                    int64_t cut_count);
 at::Tensor rgb2lab_u8(const at::Tensor& rgb_u8);
 
 // nr_metrics.hip
@@ -140,6 +150,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ssim_bwd_nhwc", &ssim_bwd_nhwc,
         "d(mean SSIM)/da from the saved maps, (N,H,W,Cp) bf16");
   m.def("preprocess_all", &preprocess_all);
+  m.def("preprocess_stats", &preprocess_stats,
+        "uint8 NHW3 -> (wb_params f32 (N,3,2), luts u8 (N,64,256), lab u8, "
+        "tile_hists i32 (N,64,256)): the statistics half of preprocess_all");
+  m.def("preprocess_apply", &preprocess_apply,
+        "(raw, lab, wb_params, luts) -> (wb, gc, he): the apply half",
+        pybind11::arg("raw"), pybind11::arg("lab"),
+        pybind11::arg("wb_params"), pybind11::arg("luts"));
+  m.def("temporal_blend", &temporal_blend,
+        "one temporal smoothing step of the WB clip points and CLAHE LUTs "
+        "over N streams, state updated in place",
+        pybind11::arg("wb"), pybind11::arg("lut"), pybind11::arg("lhist"),
+        pybind11::arg("counters"), pybind11::arg("lut_u8"),
+        pybind11::arg("wb_params"), pybind11::arg("luts"),
+        pybind11::arg("tile_hists"), pybind11::arg("alpha"),
+        pybind11::arg("cut_count"));
   m.def("rgb2lab_u8", &rgb2lab_u8,
         "uint8 NHW3 RGB -> uint8 NHW3 LAB (OpenCV 8-bit scaling)");
   m.def("nr_metrics", &nr_metrics,

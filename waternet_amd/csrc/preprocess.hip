@@ -312,32 +312,101 @@ __global__ void k_clahe_interp_lab2rgb(const uint8_t* __restrict__ lab,
 }
 
 // ---------------------------------------------------------------------------
+// Temporal smoothing of the per-frame statistics (video streams). The spec
+// is waternet_amd/data/temporal.py::temporal_blend, reproduced bit for bit:
+// one block per stream n, thread v owns grey level v.
+//   g[v]  = sum over the 64 raw tile histograms        (global L histogram)
+//   d     = sum_v |g[v] - lhist[v]|                    (exact integer)
+//   cut   = has_state == 0 || d > cut_count
+//   s     = cut ? x : s + a*(x - s)    for the 6 clip points and 64x256 LUTs
+// The three float ops are rounded one by one (no FMA contraction), as the
+// float32 NumPy expression rounds them. The decision is taken from device
+// data, so the kernel sits inside a captured graph.
+// counters: (N,3) int32 [has_state, frames, cuts].
+// ---------------------------------------------------------------------------
+
+WN_DEVFN float ema_rn(float s, float x, float a) {
+  // hipcc contracts by default, and through __fmul_rn/__fadd_rn too (they
+  // are plain operators in a header): without the pragma, on operators
+  // written here, the multiply and add become one v_fmac_f32.
+#pragma clang fp contract(off)
+  const float step = a * (x - s);
+  return s + step;
+}
+
+__global__ void k_temporal_blend(float* __restrict__ wb,         // (N,3,2)
+                                 float* __restrict__ lut,        // (N,64,256)
+                                 int* __restrict__ lhist,        // (N,256)
+                                 int* __restrict__ counters,     // (N,3)
+                                 uint8_t* __restrict__ lut_u8,   // (N,64,256)
+                                 const float* __restrict__ params,
+                                 const uint8_t* __restrict__ luts,
+                                 const int* __restrict__ thists,
+                                 float a, long long cut_count) {
+  __shared__ long long red[256];
+  const long n = blockIdx.x;
+  const int v = threadIdx.x;
+  const int* th = thists + n * 64 * 256;
+  int g = 0;
+  for (int t = 0; t < 64; ++t) g += th[t * 256 + v];
+  int* lh = lhist + n * 256;
+  const long long diff = (long long)g - (long long)lh[v];
+  red[v] = diff < 0 ? -diff : diff;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (v < s) red[v] += red[v + s];
+    __syncthreads();
+  }
+  int* c = counters + n * 3;
+  const int has = c[0];
+  const bool cut = has == 0 || red[0] > cut_count;
+  lh[v] = g;
+  for (int t = 0; t < 64; ++t) {
+    const long i = (n * 64 + t) * 256 + v;
+    const float x = (float)luts[i];
+    const float s = cut ? x : ema_rn(lut[i], x, a);
+    lut[i] = s;
+    lut_u8[i] = (uint8_t)fminf(fmaxf(rintf(s), 0.f), 255.f);
+  }
+  if (v < 6) {
+    const long i = n * 6 + v;
+    const float x = params[i];
+    wb[i] = cut ? x : ema_rn(wb[i], x, a);
+  }
+  __syncthreads();  // every thread has read c[0]
+  if (v == 0) {
+    c[0] = 1;
+    c[1] += 1;
+    if (cut && has) c[2] += 1;  // the first frame is no scene cut
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Host orchestration
 // ---------------------------------------------------------------------------
 
-std::vector<at::Tensor> preprocess_all(const at::Tensor& raw_u8) {
+namespace {
+
+struct Geom {
+  int N, H, W;
+  long HW;
+};
+
+Geom raw_geom(const at::Tensor& raw_u8, const char* who) {
   TORCH_CHECK(raw_u8.is_cuda() && raw_u8.dtype() == at::kByte &&
               raw_u8.dim() == 4 && raw_u8.size(3) == 3,
-              "raw must be (N,H,W,3) uint8 CUDA");
-  const int N = raw_u8.size(0), H = raw_u8.size(1), W = raw_u8.size(2);
-  TORCH_CHECK(H % TGRID == 0 && W % TGRID == 0,
-              "GPU CLAHE requires H,W divisible by 8 (got ", H, "x", W, ")");
-  const long HW = (long)H * W;
-  auto raw = raw_u8.contiguous();
-  auto opts = raw.options();
-  auto stream = cur_stream();
+              who, ": raw must be (N,H,W,3) uint8 CUDA");
+  Geom g{(int)raw_u8.size(0), (int)raw_u8.size(1), (int)raw_u8.size(2), 0};
+  TORCH_CHECK(g.H % TGRID == 0 && g.W % TGRID == 0,
+              "GPU CLAHE requires H,W divisible by 8 (got ", g.H, "x", g.W,
+              ")");
+  g.HW = (long)g.H * g.W;
+  return g;
+}
 
-  auto wb = at::empty_like(raw);
-  auto gc = at::empty_like(raw);
-  auto he = at::empty_like(raw);
-  auto hist = at::zeros({N, 3, 256}, opts.dtype(at::kInt));
-  auto params = at::empty({N, 3, 2}, opts.dtype(at::kFloat));
-  auto lab = at::empty_like(raw);
-  auto thists = at::empty({N, 64, 256}, opts.dtype(at::kInt));
-  auto luts = at::empty({N, 64, 256}, opts.dtype(at::kByte));
-
-  // gamma LUT: float64-exact, computed once and cached on-device (keeps the
-  // kernel sequence hipGraph-capturable: no per-call pageable H2D copy)
+// gamma LUT: float64-exact, computed once and cached on-device (keeps the
+// kernel sequence hipGraph-capturable: no per-call pageable H2D copy)
+const at::Tensor& gamma_lut(const at::Tensor& raw) {
   static at::Tensor glut;
   if (!glut.defined() || glut.device() != raw.device()) {
     uint8_t glut_host[256];
@@ -348,35 +417,190 @@ std::vector<at::Tensor> preprocess_all(const at::Tensor& raw_u8) {
     }
     glut = at::from_blob(glut_host, {256}, at::kByte).to(raw.device());
   }
+  return glut;
+}
 
-  const int nsplit = std::max(1, std::min(16, (int)(HW / 65536)));
-  hipLaunchKernelGGL(k_rgb_hist, dim3(N, nsplit), dim3(256), 0, stream,
+// RGB histograms -> (N,3,2) lo/hi clip points
+void launch_wb_stats(const at::Tensor& raw, at::Tensor& hist,
+                     at::Tensor& params, const Geom& g) {
+  auto stream = cur_stream();
+  const int nsplit = std::max(1, std::min(16, (int)(g.HW / 65536)));
+  hipLaunchKernelGGL(k_rgb_hist, dim3(g.N, nsplit), dim3(256), 0, stream,
                      raw.data_ptr<uint8_t>(),
-                     (unsigned int*)hist.data_ptr<int>(), HW, nsplit);
-  hipLaunchKernelGGL(k_wb_params, dim3(N), dim3(64), 0, stream,
+                     (unsigned int*)hist.data_ptr<int>(), g.HW, nsplit);
+  hipLaunchKernelGGL(k_wb_params, dim3(g.N), dim3(64), 0, stream,
                      (const unsigned int*)hist.data_ptr<int>(),
-                     params.data_ptr<float>(), HW);
+                     params.data_ptr<float>(), g.HW);
+}
+
+void launch_wb_gc_apply(const at::Tensor& raw, const at::Tensor& params,
+                        at::Tensor& wb, at::Tensor& gc, const Geom& g) {
+  const at::Tensor& glut = gamma_lut(raw);
   hipLaunchKernelGGL(k_wb_gc_apply,
-                     dim3(grid1d(HW, TPB, 1024), N),
-                     dim3(256), 0, stream, raw.data_ptr<uint8_t>(),
+                     dim3(grid1d(g.HW, TPB, 1024), g.N),
+                     dim3(256), 0, cur_stream(), raw.data_ptr<uint8_t>(),
                      params.data_ptr<float>(), glut.data_ptr<uint8_t>(),
-                     wb.data_ptr<uint8_t>(), gc.data_ptr<uint8_t>(), HW);
-  const long total = (long)N * HW;
+                     wb.data_ptr<uint8_t>(), gc.data_ptr<uint8_t>(), g.HW);
+}
+
+// LAB image, raw tile histograms (k_clahe_lut only reads them) and tile LUTs
+void launch_clahe_stats(const at::Tensor& raw, at::Tensor& lab,
+                        at::Tensor& thists, at::Tensor& luts, const Geom& g) {
+  auto stream = cur_stream();
+  const long total = (long)g.N * g.HW;
   hipLaunchKernelGGL(k_rgb2lab,
                      dim3(grid1d(total)), dim3(256), 0, stream, raw.data_ptr<uint8_t>(),
                      lab.data_ptr<uint8_t>(), total);
-  hipLaunchKernelGGL(k_clahe_hist, dim3(N, 64), dim3(256), 0, stream,
+  hipLaunchKernelGGL(k_clahe_hist, dim3(g.N, 64), dim3(256), 0, stream,
                      lab.data_ptr<uint8_t>(),
-                     (unsigned int*)thists.data_ptr<int>(), H, W);
-  const int tileArea = (H / TGRID) * (W / TGRID);
+                     (unsigned int*)thists.data_ptr<int>(), g.H, g.W);
+  const int tileArea = (g.H / TGRID) * (g.W / TGRID);
   const int clip = std::max((int)(0.1 * tileArea / 256.0), 1);
-  hipLaunchKernelGGL(k_clahe_lut, dim3(N * 64), dim3(256), 0, stream,
+  hipLaunchKernelGGL(k_clahe_lut, dim3(g.N * 64), dim3(256), 0, stream,
                      (unsigned int*)thists.data_ptr<int>(),
                      luts.data_ptr<uint8_t>(), tileArea, clip);
+}
+
+void launch_clahe_apply(const at::Tensor& lab, const at::Tensor& luts,
+                        at::Tensor& he, const Geom& g) {
   hipLaunchKernelGGL(k_clahe_interp_lab2rgb,
-                     dim3(grid1d(HW, TPB, 1024), N),
-                     dim3(256), 0, stream, lab.data_ptr<uint8_t>(),
-                     luts.data_ptr<uint8_t>(), he.data_ptr<uint8_t>(), H, W);
+                     dim3(grid1d(g.HW, TPB, 1024), g.N),
+                     dim3(256), 0, cur_stream(), lab.data_ptr<uint8_t>(),
+                     luts.data_ptr<uint8_t>(), he.data_ptr<uint8_t>(), g.H,
+                     g.W);
+}
+
+}  // namespace
+
+// The per-image path: statistics and apply interleaved, WB before CLAHE.
+std::vector<at::Tensor> preprocess_all(const at::Tensor& raw_u8) {
+  const Geom g = raw_geom(raw_u8, "preprocess_all");
+  auto raw = raw_u8.contiguous();
+  auto opts = raw.options();
+
+  auto wb = at::empty_like(raw);
+  auto gc = at::empty_like(raw);
+  auto he = at::empty_like(raw);
+  auto hist = at::zeros({g.N, 3, 256}, opts.dtype(at::kInt));
+  auto params = at::empty({g.N, 3, 2}, opts.dtype(at::kFloat));
+  auto lab = at::empty_like(raw);
+  auto thists = at::empty({g.N, 64, 256}, opts.dtype(at::kInt));
+  auto luts = at::empty({g.N, 64, 256}, opts.dtype(at::kByte));
+  if (raw.numel() == 0) return {wb, gc, he};
+
+  launch_wb_stats(raw, hist, params, g);
+  launch_wb_gc_apply(raw, params, wb, gc, g);
+  launch_clahe_stats(raw, lab, thists, luts, g);
+  launch_clahe_apply(lab, luts, he, g);
   HIP_CHECK_LAST();
   return {wb, gc, he};
+}
+
+// The statistics half: everything preprocess_all derives from the image
+// before it transforms a pixel. -> (wb_params f32 (N,3,2), luts u8
+// (N,64,256), lab u8 (N,H,W,3), tile_hists i32 (N,64,256), unclipped).
+std::vector<at::Tensor> preprocess_stats(const at::Tensor& raw_u8) {
+  const Geom g = raw_geom(raw_u8, "preprocess_stats");
+  auto raw = raw_u8.contiguous();
+  auto opts = raw.options();
+  auto hist = at::zeros({g.N, 3, 256}, opts.dtype(at::kInt));
+  auto params = at::empty({g.N, 3, 2}, opts.dtype(at::kFloat));
+  auto lab = at::empty_like(raw);
+  auto thists = at::empty({g.N, 64, 256}, opts.dtype(at::kInt));
+  auto luts = at::empty({g.N, 64, 256}, opts.dtype(at::kByte));
+  if (raw.numel() == 0) return {params, luts, lab, thists};
+  launch_wb_stats(raw, hist, params, g);
+  launch_clahe_stats(raw, lab, thists, luts, g);
+  HIP_CHECK_LAST();
+  return {params, luts, lab, thists};
+}
+
+// The apply half, from any clip points and LUTs of the right shape (the
+// frame's own, or the temporally smoothed ones). -> (wb, gc, he).
+std::vector<at::Tensor> preprocess_apply(const at::Tensor& raw_u8,
+                                         const at::Tensor& lab,
+                                         const at::Tensor& wb_params,
+                                         const at::Tensor& luts) {
+  const Geom g = raw_geom(raw_u8, "preprocess_apply");
+  auto raw = raw_u8.contiguous();
+  TORCH_CHECK(dense_like(lab, raw),
+              "preprocess_apply: lab must be a contiguous uint8 tensor of "
+              "raw's shape and device");
+  TORCH_CHECK(dense(wb_params, at::kFloat, 3) && wb_params.size(0) == g.N &&
+              wb_params.size(1) == 3 && wb_params.size(2) == 2 &&
+              wb_params.device() == raw.device(),
+              "preprocess_apply: wb_params must be (N,3,2) float32 "
+              "contiguous on raw's device");
+  TORCH_CHECK(dense(luts, at::kByte, 3) && luts.size(0) == g.N &&
+              luts.size(1) == 64 && luts.size(2) == 256 &&
+              luts.device() == raw.device(),
+              "preprocess_apply: luts must be (N,64,256) uint8 contiguous "
+              "on raw's device");
+  auto wb = at::empty_like(raw);
+  auto gc = at::empty_like(raw);
+  auto he = at::empty_like(raw);
+  if (raw.numel() == 0) return {wb, gc, he};
+  launch_wb_gc_apply(raw, wb_params, wb, gc, g);
+  launch_clahe_apply(lab, luts, he, g);
+  HIP_CHECK_LAST();
+  return {wb, gc, he};
+}
+
+// One k_temporal_blend step over N streams, state updated in place. After
+// it, `wb` holds the clip points and `lut_u8` the LUTs preprocess_apply is
+// to use for this frame.
+void temporal_blend(at::Tensor& wb, at::Tensor& lut, at::Tensor& lhist,
+                    at::Tensor& counters, at::Tensor& lut_u8,
+                    const at::Tensor& wb_params, const at::Tensor& luts,
+                    const at::Tensor& tile_hists, double alpha,
+                    int64_t cut_count) {
+  TORCH_CHECK(dense(wb_params, at::kFloat, 3) && wb_params.size(1) == 3 &&
+              wb_params.size(2) == 2,
+              "temporal_blend: wb_params must be (N,3,2) float32 contiguous "
+              "CUDA");
+  const long N = wb_params.size(0);
+  auto shaped = [&](const at::Tensor& t, at::ScalarType dt,
+                    std::initializer_list<long> tail) {
+    if (!dense(t, dt, (int)tail.size() + 1) || t.size(0) != N ||
+        t.device() != wb_params.device())
+      return false;
+    int d = 1;
+    for (long e : tail)
+      if (t.size(d++) != e) return false;
+    return true;
+  };
+  TORCH_CHECK(shaped(luts, at::kByte, {64, 256}),
+              "temporal_blend: luts must be (N,64,256) uint8 contiguous on "
+              "wb_params' device");
+  TORCH_CHECK(shaped(tile_hists, at::kInt, {64, 256}),
+              "temporal_blend: tile_hists must be (N,64,256) int32 "
+              "contiguous on wb_params' device");
+  TORCH_CHECK(shaped(wb, at::kFloat, {3, 2}),
+              "temporal_blend: state wb must be (N,3,2) float32 contiguous "
+              "on wb_params' device");
+  TORCH_CHECK(shaped(lut, at::kFloat, {64, 256}),
+              "temporal_blend: state lut must be (N,64,256) float32 "
+              "contiguous on wb_params' device");
+  TORCH_CHECK(shaped(lhist, at::kInt, {256}),
+              "temporal_blend: state lhist must be (N,256) int32 contiguous "
+              "on wb_params' device");
+  TORCH_CHECK(shaped(counters, at::kInt, {3}),
+              "temporal_blend: state counters must be (N,3) int32 "
+              "contiguous on wb_params' device");
+  TORCH_CHECK(shaped(lut_u8, at::kByte, {64, 256}),
+              "temporal_blend: state lut_u8 must be (N,64,256) uint8 "
+              "contiguous on wb_params' device");
+  TORCH_CHECK(alpha > 0.0 && alpha <= 1.0,
+              "temporal_blend: alpha must be in (0,1], got ", alpha);
+  TORCH_CHECK(cut_count >= 0,
+              "temporal_blend: cut_count must be >= 0, got ", cut_count);
+  if (N == 0) return;
+  hipLaunchKernelGGL(k_temporal_blend, dim3((unsigned)N), dim3(256), 0,
+                     cur_stream(), wb.data_ptr<float>(),
+                     lut.data_ptr<float>(), lhist.data_ptr<int>(),
+                     counters.data_ptr<int>(), lut_u8.data_ptr<uint8_t>(),
+                     wb_params.data_ptr<float>(), luts.data_ptr<uint8_t>(),
+                     tile_hists.data_ptr<int>(), (float)alpha,
+                     (long long)cut_count);
+  HIP_CHECK_LAST();
 }

@@ -37,6 +37,16 @@ def white_balance_transform(im_rgb: np.ndarray) -> np.ndarray:
     satLo = satHi = 0.005 * (max_channel_sum / channel_sum) for RGB;
     [0.001, 0.005] for grayscale.
     """
+    return white_balance_apply(im_rgb, white_balance_params(im_rgb))
+
+
+def white_balance_params(im_rgb: np.ndarray) -> np.ndarray:
+    """The per-image statistics of white_balance_transform: (p,2) float64
+    [lo, hi] clip points per channel (p = 3 for HWC, 1 for grayscale).
+
+    They are the whole white-balance state: the stretch runs from `bottom`
+    = clip(min, lo, hi) to `top` = clip(max, lo, hi), and a quantile lies
+    within [min, max], so bottom == lo and top == hi."""
     if im_rgb.ndim == 3:
         h, w, p = im_rgb.shape
         chan_sums = np.array(
@@ -56,14 +66,12 @@ def white_balance_transform(im_rgb: np.ndarray) -> np.ndarray:
         flat = im_rgb.reshape(1, h * w)
 
     # uint8 data: quantiles are order statistics over a 256-bin histogram
-    # (O(n) bincount instead of np.quantile's O(n log n) sort) and the
-    # clip+stretch is a 256-entry float64 LUT gather — BIT-identical to
-    # the per-pixel float64 formula (verified against the direct
+    # (O(n) bincount instead of np.quantile's O(n log n) sort) —
+    # BIT-identical to np.quantile (verified against the direct
     # np.quantile composition by test_white_balance_reference_semantics
     # and the hypothesis fuzz).
     n = flat.shape[1]
-    out = np.empty((p, n), dtype=np.float64)
-    vals = np.arange(256, dtype=np.float64)
+    params = np.empty((p, 2), dtype=np.float64)
     for ch in range(p):
         lo_q, hi_q = sat_lo[ch], 1.0 - sat_hi[ch]
         # Degenerate channels (a zero channel sum makes the sat ratio
@@ -74,19 +82,29 @@ def white_balance_transform(im_rgb: np.ndarray) -> np.ndarray:
             lo_q, hi_q = 0.0, 1.0
         hist = np.bincount(flat[ch], minlength=256)
         cum = np.cumsum(hist)
-        lo_v = _quantile_from_hist(cum, n, lo_q)
-        hi_v = _quantile_from_hist(cum, n, hi_q)
-        nz = np.nonzero(hist)[0]
-        vmin, vmax = float(nz[0]), float(nz[-1])
-        bottom = min(max(vmin, lo_v), hi_v)  # clip is monotone
-        top = min(max(vmax, lo_v), hi_v)
-        scale = 255.0 / (top - bottom) if top > bottom else 0.0
-        lut = (np.clip(vals, lo_v, hi_v) - bottom) * scale
-        out[ch] = lut[flat[ch]]
+        params[ch, 0] = _quantile_from_hist(cum, n, lo_q)
+        params[ch, 1] = _quantile_from_hist(cum, n, hi_q)
+    return params
 
-    if im_rgb.ndim == 3:
-        return out.T.reshape(h, w, p).astype(np.uint8)
-    return out.reshape(h, w).astype(np.uint8)
+
+def white_balance_apply(im_rgb: np.ndarray, params: np.ndarray) -> np.ndarray:
+    """Clip each channel to its [lo, hi] and stretch to [0,255], truncating
+    to uint8. `params` is (p,2), as white_balance_params returns it (any
+    float dtype: float32 clip points are widened exactly, as the GPU apply
+    kernel reads them).
+
+    The clip+stretch of uint8 data is a 256-entry float64 LUT gather —
+    BIT-identical to the per-pixel float64 formula."""
+    params = np.asarray(params, dtype=np.float64)
+    vals = np.arange(256, dtype=np.float64)
+    planes = im_rgb[..., None] if im_rgb.ndim == 2 else im_rgb
+    out = np.empty(planes.shape, dtype=np.float64)
+    for ch in range(planes.shape[2]):
+        lo_v, hi_v = float(params[ch, 0]), float(params[ch, 1])
+        scale = 255.0 / (hi_v - lo_v) if hi_v > lo_v else 0.0
+        lut = (np.clip(vals, lo_v, hi_v) - lo_v) * scale
+        out[..., ch] = lut[planes[..., ch]]
+    return out.reshape(im_rgb.shape).astype(np.uint8)
 
 
 def _quantile_from_hist(cum: np.ndarray, n: int, q: float) -> float:
@@ -220,12 +238,29 @@ def clahe_u8(
          cdf[i] * 255 / tileArea).
       3. Per pixel: bilinear interpolation between the 4 surrounding tile LUTs.
     """
+    return clahe_apply(src, clahe_luts(src, clip_limit, tile_grid), tile_grid)
+
+
+def _clahe_pad(src: np.ndarray, tile_grid: Tuple[int, int]) -> np.ndarray:
+    """Pad to a multiple of the grid (reflect-101, like cv2.copyMakeBorder)."""
     h, w = src.shape
     ty_n, tx_n = tile_grid
-    # Pad to a multiple of the grid (reflect-101, like cv2.copyMakeBorder)
     ph = (ty_n - h % ty_n) % ty_n
     pw = (tx_n - w % tx_n) % tx_n
-    img = np.pad(src, ((0, ph), (0, pw)), mode="reflect") if (ph or pw) else src
+    if not (ph or pw):
+        return src
+    return np.pad(src, ((0, ph), (0, pw)), mode="reflect")
+
+
+def clahe_luts(
+    src: np.ndarray, clip_limit: float = 0.1,
+    tile_grid: Tuple[int, int] = (8, 8), return_hists: bool = False,
+):
+    """Steps 1-2 of clahe_u8, the per-image statistics: the (ty, tx, 256)
+    uint8 tile LUTs. With return_hists also the (ty, tx, 256) int64 tile
+    histograms of the padded image as counted, before clipping."""
+    ty_n, tx_n = tile_grid
+    img = _clahe_pad(src, tile_grid)
     H, W = img.shape
     th, tw = H // ty_n, W // tx_n
     tile_area = th * tw
@@ -240,6 +275,7 @@ def clahe_u8(
     for ti in range(ty_n):
         for tj in range(tx_n):
             hist[ti, tj] = np.bincount(tiles[ti, tj], minlength=256)
+    raw_hist = hist.copy() if return_hists else None
 
     if clip > 0:
         for ti in range(ty_n):
@@ -260,6 +296,19 @@ def clahe_u8(
     cdf = np.cumsum(hist, axis=-1)
     # cv::saturate_cast<uchar>(float) rounds half-to-even (cvRound)
     luts = np.clip(np.rint(cdf * lut_scale), 0, 255).astype(np.uint8)
+    return (luts, raw_hist) if return_hists else luts
+
+
+def clahe_apply(
+    src: np.ndarray, luts: np.ndarray, tile_grid: Tuple[int, int] = (8, 8)
+) -> np.ndarray:
+    """Step 3 of clahe_u8: map `src` through (ty, tx, 256) uint8 tile LUTs
+    (its own, from clahe_luts, or any others of that shape)."""
+    h, w = src.shape
+    ty_n, tx_n = tile_grid
+    img = _clahe_pad(src, tile_grid)
+    H, W = img.shape
+    th, tw = H // ty_n, W // tx_n
 
     # Bilinear interpolation of per-tile LUT outputs
     ys = np.arange(H, dtype=np.float64)

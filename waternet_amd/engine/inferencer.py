@@ -16,7 +16,9 @@ import numpy as np
 import torch
 
 from waternet_amd.ops import ext
-from waternet_amd.ops.preprocess import gpu_transform_batch
+from waternet_amd.ops.preprocess import (gpu_transform_batch,
+                                         gpu_transform_stream,
+                                         new_temporal_state)
 
 
 def pad8(rgb_u8: np.ndarray):
@@ -37,7 +39,11 @@ def pad8(rgb_u8: np.ndarray):
 
 class InferenceEngine:
     def __init__(self, model, height, width, device="cuda:0",
-                 use_graph=True):
+                 use_graph=True, temporal_alpha=None, scene_cut=0.5):
+        """temporal_alpha in (0,1] turns on temporally smoothed WB/CLAHE
+        statistics (waternet_amd/data/temporal.py) for a video stream, with
+        a state reset where the L histogram moves by more than scene_cut of
+        its range; None is the per-frame pipeline."""
         self.model = model.eval()
         self.device = torch.device(device)
         self.h, self.w = height, width
@@ -46,13 +52,26 @@ class InferenceEngine:
         self.out_static = None
         self._graph = None
         self._use_graph = use_graph and height % 8 == 0 and width % 8 == 0
+        self._temporal = None
+        if temporal_alpha is not None:
+            from waternet_amd.data.temporal import (check_alpha,
+                                                    scene_cut_count)
+
+            # allocated here, outside capture: the state outlives replays
+            self._temporal = new_temporal_state(1, self.device)
+            self._alpha = check_alpha(temporal_alpha)
+            self._cut_count = scene_cut_count(scene_cut, height, width)
 
     @torch.no_grad()
     def _body(self):
         from waternet_amd.engine.native import waternet_forward_from_inputs
 
         raw = self.raw_static
-        wb, gc, he = gpu_transform_batch(raw)
+        if self._temporal is None:
+            wb, gc, he = gpu_transform_batch(raw)
+        else:
+            wb, gc, he = gpu_transform_stream(raw, self._temporal,
+                                              self._alpha, self._cut_count)
         e = ext()
         # he fills the ce slot (reference inference.py:191 -> net.py:99);
         # full-NHWC: fused uint8 cat-fold -> convs -> fused u8 postprocess,
@@ -79,6 +98,23 @@ class InferenceEngine:
             print(f"[inferencer] graph capture failed, eager: {e!r}",
                   file=sys.stderr)
             self._use_graph = False
+        # warm-up and capture ran _body on whatever the buffer held: the
+        # first real frame is frame 0
+        self.reset_temporal()
+
+    def reset_temporal(self):
+        """Start a new stream: the next frame initialises the state. One
+        memset of [has_state, frames, cuts], outside the graph."""
+        if self._temporal is not None:
+            self._temporal["counters"].zero_()
+
+    def temporal_counters(self) -> dict:
+        """{frames, cuts} of the current stream (one host read)."""
+        if self._temporal is None:
+            raise RuntimeError("temporal_counters() needs an engine built "
+                               "with temporal_alpha")
+        _, frames, cuts = self._temporal["counters"][0].tolist()
+        return {"frames": frames, "cuts": cuts}
 
     @torch.no_grad()
     def infer_frame(self, rgb_u8: np.ndarray) -> np.ndarray:
