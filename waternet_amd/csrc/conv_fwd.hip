@@ -13,6 +13,10 @@
 //   - k_conv_patch<KS,BN,CC>: big-M k3/k5/k7 layers with 64/128 channels and
 //     H, W multiples of 16: a 16x16 output-pixel tile per block, the input
 //     patch staged into LDS once and the taps taken by shifted reads.
+//   - k_conv_tile<CC,IMG7,SLAB>: the deep k3 layers (Cp 128..512 on 56^2 ..
+//     7^2 images): a 14x14 output-pixel tile (or four 7x7 images) and one
+//     CC-channel chunk of the input patch resident per block, chunks summed
+//     through the split-K slabs.
 //   - k_splitk_finalize<GZ>: sums the split-K slabs, bias + activation.
 // The weight-gradient kernels are in conv_wgrad.hip, weight packing in
 // conv_pack.hip; conv_common.h has the notes and host helpers they share.
@@ -821,6 +825,343 @@ __global__ __launch_bounds__(
                         n0 + wc * (BN / G::WNW), lane, out);
 }
 
+// ---------------------------------------------------------------------------
+// Tile-resident conv for the deep k3 layers (Cp 128..512 on 28^2, 14^2, 7^2
+// images). The split-K igemm re-stages a 128x32 A tile for each of the 9 taps
+// and streams every weight through every block; here a block owns 196 output
+// pixels x 128 output channels x one CC-channel chunk of the reduction:
+//   - rows: a 14x14 output-pixel tile of one image (14 divides 28, 14, 56),
+//     or, for 7x7 images, four whole images of 49 pixels each (their GEMM rows
+//     are consecutive). 196 rows = 13 fragments of 16, the last masked past
+//     row 195.
+//   - A: the 16x16-pixel input patch (or four 9x9 patches) of the chunk is
+//     staged ONCE as [pixel][CC] rows; the fragment of tap (dy, dx) is the
+//     tap-0 read moved by dy*PW + dx pixel rows, as in k_conv_patch.
+//   - B: the fragment-major 3-deep ring of k_conv_patch with 64-K tiles (two
+//     32-K sub-tiles per barrier). K order: tap-major, channel inner within
+//     the chunk.
+//   - reduction over the gz = Cp / CC chunks: gz == 1 writes bf16 through
+//     bias_act; gz > 1 writes fp32 slabs that k_splitk_finalize<gz> sums in
+//     slab order (no atomics: the bits repeat from call to call). The sums
+//     are grouped by chunk, not by contiguous rsc range as in the split-K
+//     igemm, so outputs differ from that tier at fp32-rounding level.
+//   - 512 threads = 8 waves as 2(M) x 4(N): a wave owns 7 (6 for the second
+//     M half) row fragments x 2 channel fragments.
+//   - swizzle: 16 consecutive GEMM rows are not 16 consecutive patch pixels
+//     (a tile row ends after 14 pixels, an image row after 7), so CpSwz does
+//     not apply. Every patch pixel has a PHASE that grows by one per GEMM row
+//     of the tile: (px + 6*py) & 7 with a 16-pixel pitch (14 + 2*16 = 6 mod
+//     8 steps back to px = 0 of the next row), (px + 7*py + img) & 7 for the
+//     9x9 patches; a tap shift adds a constant to all 16 rows of a fragment.
+//     The chunk index is XORed with the phase as CpSwz does with the pixel
+//     index, so the 8 rows ds_read_b128 serves together in one k-group land
+//     on 8 distinct columns. tile_frag_conflict_free enumerates it for every
+//     fragment, tap and k-step of each instantiation.
+//   - block -> work: slice-major on a 1-D grid (block = slice * tiles +
+//     tile, a slice being an (N block, chunk) pair). A map that gave the
+//     blocks of equal blockIdx % 8 the same slices, to fetch a weight slice
+//     once per XCD, measured equal or slower on every class and was dropped
+//     (docs/HEADROOM.md).
+// ---------------------------------------------------------------------------
+
+template <bool IMG7>
+struct TileMap {
+  static constexpr int ROWS = 196;   // GEMM rows of a tile
+  static constexpr int NFRAG = 13;   // 16-row fragments that hold them
+  static constexpr int PW = IMG7 ? 9 : 16;          // patch row pitch
+  static constexpr int NPX = IMG7 ? 4 * 81 : 256;   // staged patch pixels
+  static constexpr int KDY = IMG7 ? 7 : 6;  // phase step of a patch row
+  // tile row -> patch pixel its tap (0, 0) reads; rows 196..207 of the last
+  // fragment continue the pattern past the staged pixels (masked outputs)
+  static constexpr int pix(int r) {
+    return IMG7 ? (r / 49) * 81 + (r % 49) / 7 * 9 + r % 7
+                : (r / 14) * 16 + r % 14;
+  }
+  static constexpr int phase(int pix) {
+    return IMG7 ? (pix / 81 + (pix % 81) / 9 * 7 + pix % 9) & 7
+                : ((pix >> 4) * 6 + (pix & 15)) & 7;
+  }
+  // image pixels past the staged ones that the masked rows may read
+  static constexpr int ALLOCPX = (pix(NFRAG * 16 - 1) + 2 * PW + 2 + 8) / 8 * 8;
+};
+// chunk XOR of a phase: above chunk bit 0 as CpSwz (CC = 64: two pixels share
+// a 256 B bank row and the phase's bit 0 is the pixel's)
+constexpr int tile_phase_xor(int ph, int CC) {
+  return CC == 64 ? ((ph >> 1) & 3) << 1 : (ph & 7) << 1;
+}
+template <bool IMG7>
+struct TileSwz {
+  static constexpr int chunk_xor(int pix, int CC) {
+    return tile_phase_xor(TileMap<IMG7>::phase(pix), CC);
+  }
+};
+template <bool IMG7>
+using TileImage = PatchImage<TileSwz<IMG7>>;
+
+// Fragment `fr`'s A reads: at every tap and k-step the address the kernel
+// forms (phase of lane row li at tap (dy, dx) = li + dx + KDY*dy, k-step by
+// XOR) is the image's, stays inside the allocation, and is conflict-free in
+// each ds_read_b128 lane group.
+template <bool IMG7>
+constexpr bool tile_frag_conflict_free(int CC, int fr) {
+  using Map = TileMap<IMG7>;
+  for (int tap = 0; tap < 9; ++tap)
+    for (int kb = 0; kb < CC / 32; ++kb)
+      for (int g = 0; g < 4; ++g) {
+        const int dy = tap / 3, dx = tap % 3;
+        unsigned used = 0;
+        for (int l = 0; l < 64; ++l) {
+          const int m = l & 31;
+          const bool first =
+              m < 4 || (m >= 12 && m < 16) || (m >= 20 && m < 28);
+          if ((l >> 5) * 2 + (first ? 0 : 1) != g) continue;
+          const int pixel = Map::pix(fr * 16 + (l & 15)) + dy * Map::PW + dx;
+          const int a = TileImage<IMG7>::off(pixel, kb * 4 + (l >> 4), CC);
+          const int ph = ((l & 15) + dx + Map::KDY * dy) & 7;
+          const int mine =
+              (pixel * CC * 2 + (((l >> 4) ^ tile_phase_xor(ph, CC)) << 4)) ^
+              (kb * 64);
+          if (a != mine || a + 16 > Map::ALLOCPX * CC * 2) return false;
+          const unsigned bit = 1u << ((a / 16) % 16);
+          if (used & bit) return false;
+          used |= bit;
+        }
+        if (used != 0xffffu) return false;
+      }
+  return true;
+}
+// one constant evaluation per fragment
+template <bool IMG7, int CC, int FR = TileMap<IMG7>::NFRAG - 1>
+struct TileFragProof {
+  static constexpr bool value = tile_frag_conflict_free<IMG7>(CC, FR) &&
+                                TileFragProof<IMG7, CC, FR - 1>::value;
+};
+template <bool IMG7, int CC>
+struct TileFragProof<IMG7, CC, -1> {
+  static constexpr bool value = true;
+};
+
+template <int CC, bool IMG7>
+struct ConvTileGeo {
+  using Map = TileMap<IMG7>;
+  static constexpr int THREADS = 512;
+  static constexpr int BN = 128;
+  static constexpr int WMW = 2, WNW = 4;  // wave grid
+  static constexpr int FM = 7, FN = BN / WNW / 16;
+  static constexpr int PSLOTS = Map::NPX * (CC / 8);
+  static constexpr int PINSTR = (PSLOTS + 63) / 64;  // wave-wide glds
+  static constexpr int SP = (PINSTR * 64 + THREADS - 1) / THREADS;
+  static constexpr int PBYTES = Map::ALLOCPX * CC * 2;
+  static constexpr int KSTEP = 64;        // K of a staged B tile
+  static constexpr int LB = BN * KSTEP;   // B tile elems: two 32-K sub-tiles
+  static constexpr int RING = 3;
+  static constexpr int AHEAD = RING - 2;
+  static constexpr int GPS = 2;           // glds per thread per B tile
+  static constexpr int SPT = CC / KSTEP;  // B tiles per tap
+  static constexpr int NK = 9 * SPT;
+  static constexpr int LDS_BYTES = PBYTES + RING * LB * (int)sizeof(bf16_t);
+  static_assert(PINSTR * 1024 <= PBYTES && PBYTES % 1024 == 0);
+  static_assert(LDS_BYTES <= 160 * 1024);
+  static_assert(BN * 4 == THREADS, "one B slot per thread and sub-tile");
+};
+
+// tile row -> GEMM row; rows past the tile's 196 map to M (not stored)
+template <bool IMG7>
+struct TileRows {
+  long m00, M;
+  int W;
+  WN_DEVFN long operator()(int r) const {
+    if (r >= TileMap<IMG7>::ROWS) return M;
+    if constexpr (IMG7)
+      return m00 + r;
+    else
+      return m00 + (long)(r / 14) * W + (r % 14);
+  }
+};
+
+template <int CC, bool IMG7, bool SLAB>
+__global__ __launch_bounds__(512, 2) void k_conv_tile(
+    const bf16_t* __restrict__ X,   // (N, H, W, Cp), Cp = gz * CC
+    const bf16_t* __restrict__ Wp,  // [Kp][9*Cp]
+    const float* __restrict__ Bias,
+    bf16_t* __restrict__ Y,         // (N, H, W, Kp), Kp % 128 == 0
+    int N, int H, int W, int Cp, int log2Cp, int Kp, int Klog, int act,
+    const bf16_t* __restrict__ Zero16,
+    float* __restrict__ Y32,  // SLAB: [Cp / CC][M][Kp] (contract: ConvOut)
+    int tiles) {
+  static_assert(WN_MFMA_KMAP == 0, "glds staging assumes KMAP 0");
+  using G = ConvTileGeo<CC, IMG7>;
+  using Map = TileMap<IMG7>;
+  using Img = TileImage<IMG7>;
+  constexpr int PW = Map::PW, NPX = Map::NPX, SP = G::SP;
+  constexpr int FM = G::FM, FN = G::FN, LB = G::LB, RING = G::RING;
+  constexpr int AHEAD = G::AHEAD, SPT = G::SPT, NK = G::NK;
+  constexpr int THREADS = G::THREADS;  // local: see k_conv_igemm8
+  static_assert(CC == 64 || CC == 128);
+  static_assert(Img::linear(NPX, CC), "glds slot order != image chunk order");
+  static_assert(TileFragProof<IMG7, CC>::value,
+                "fragment read: bank conflict or address mismatch");
+  const int KG = 9 * Cp;
+  const long M = (long)N * H * W;
+
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* lP = smem;                                           // patch
+  bf16_t* lB = reinterpret_cast<bf16_t*>(smem + G::PBYTES);  // RING x LB
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int wr = __builtin_amdgcn_readfirstlane(wid >> 2);
+  const int wc = wid & 3;
+
+  // block -> (weight slice, tile), block-uniform; a slice is an (N block,
+  // chunk) pair
+  const int gy = Kp / G::BN;
+  const int slice = blockIdx.x / tiles;
+  const int tile = blockIdx.x - slice * tiles;
+  const int n0 = (slice % gy) * G::BN;
+  const int z = slice / gy;
+  const int c0 = z * CC;
+
+  // tile -> first image / first output pixel
+  int nImg, oy0 = 0, ox0 = 0;
+  if constexpr (IMG7) {
+    nImg = tile * 4;
+  } else {
+    const int tilesX = W / 14, tilesY = H / 14;
+    nImg = tile / (tilesX * tilesY);
+    const int t = tile - nImg * (tilesX * tilesY);
+    oy0 = (t / tilesX) * 14;
+    ox0 = (t - (t / tilesX) * tilesX) * 14;
+  }
+
+  // The patch: as in k_conv_patch, every lane of every issued wave-wide glds
+  // sources its pixel's (swizzled) chunk or Zero16 (halo outside the image,
+  // images past N, surplus slots).
+#pragma unroll
+  for (int s = 0; s < SP; ++s) {
+    const int sg = tid + s * THREADS;
+    if ((sg >> 6) < G::PINSTR) {  // wave-uniform
+      const int pix = Img::slot_pix(sg, CC);
+      int n, iy, ix;
+      if constexpr (IMG7) {
+        const int img = pix / 81, q = pix - img * 81;
+        n = nImg + img;
+        iy = q / 9 - 1;
+        ix = q - (q / 9) * 9 - 1;
+      } else {
+        n = nImg;
+        iy = oy0 + (pix >> 4) - 1;
+        ix = ox0 + (pix & 15) - 1;
+      }
+      const bf16_t* src = Zero16;
+      if (pix < NPX && n < N && iy >= 0 && iy < H && ix >= 0 && ix < W)
+        src = X + (((long)n * H + iy) * W + ix) * Cp + c0 +
+              Img::slot_chunk(sg, CC) * 8;
+      glds16(src, reinterpret_cast<bf16_t*>(lP + sg * 16));
+    }
+  }
+
+  // B tile g: taps' CC-channel chunk in 64-K pieces, two fragment-major
+  // 32-K sub-tiles; every thread issues GPS = 2 glds (k < Kp: Kp % 128 == 0)
+  const FragSlot bf = frag_slot<false>(tid);
+  const bf16_t* bSrc = Wp + (long)(n0 + bf.row) * KG + c0 + bf.koff;
+  auto stage_b = [&](int buf, int g) {
+    const int tap = g / SPT, h = g - tap * SPT;
+    const bf16_t* src = bSrc + tap * Cp + h * G::KSTEP;
+    glds16(src, lB + buf * LB + tid * 8);
+    glds16(src + 32, lB + buf * LB + G::BN * 32 + tid * 8);
+  };
+
+  f32x4 acc[FM][FN];
+#pragma unroll
+  for (int a = 0; a < FM; ++a)
+#pragma unroll
+    for (int b = 0; b < FN; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int lg = lane >> 4, li = lane & 15;
+  // the second M half has 6 fragments: 13 in all
+  const int nfm = wr == 0 ? FM : Map::NFRAG - FM;
+  // byte offset of this lane's row of each fragment at tap (0, 0), chunk 0
+  int aPix[FM];
+#pragma unroll
+  for (int fm = 0; fm < FM; ++fm) {
+    const int r = min((wr * FM + fm) * 16 + li, Map::NFRAG * 16 - 1);
+    aPix[fm] = Map::pix(r) * CC * 2;
+  }
+
+  for (int t = 0; t < RING - 1 && t < NK; ++t) stage_b(t, t);
+  wait_vmcnt<0>();
+  __builtin_amdgcn_s_barrier();
+
+  int g = 0;
+  for (int tap = 0; tap < 9; ++tap) {
+    const int dy = tap / 3, dx = tap - dy * 3;
+    // k-step 0 addresses; k-step kb flips chunk bits 2-3 = address bits 6-7
+    const int ph = (li + dx + Map::KDY * dy) & 7;
+    const int tapOff =
+        (dy * PW + dx) * CC * 2 + ((lg ^ tile_phase_xor(ph, CC)) << 4);
+    unsigned aAd[FM];
+#pragma unroll
+    for (int fm = 0; fm < FM; ++fm) aAd[fm] = (unsigned)(aPix[fm] + tapOff);
+#pragma unroll
+    for (int h = 0; h < SPT; ++h, ++g) {
+      const int b = g % RING;
+      if (g + RING - 1 < NK) stage_b((b + RING - 1) % RING, g + RING - 1);
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const int kb = h * 2 + s;
+        bf16x8 aF[FM], bF[FN];
+#pragma unroll
+        for (int fn = 0; fn < FN; ++fn)
+          bF[fn] = *reinterpret_cast<const bf16x8*>(
+              lB + b * LB + s * (G::BN * 32) +
+              (((wc * FN + fn) * 4 + lg) * 16 + li) * 8);
+#pragma unroll
+        for (int ph2 = 0; ph2 < 2; ++ph2) {
+          const int f0 = ph2 * 4, f1 = ph2 ? FM : 4;
+#pragma unroll
+          for (int fm = f0; fm < f1; ++fm)
+            if (fm < nfm)
+              aF[fm] = *reinterpret_cast<const bf16x8*>(
+                  lP + (aAd[fm] ^ (unsigned)(kb * 64)));
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          __builtin_amdgcn_sched_barrier(0);
+          __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+          for (int fm = f0; fm < f1; ++fm)
+            if (fm < nfm) {
+#pragma unroll
+              for (int fn = 0; fn < FN; ++fn)
+                acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                    aF[fm], bF[fn], acc[fm][fn], 0, 0, 0);
+            }
+          __builtin_amdgcn_s_setprio(0);
+        }
+      }
+      if (g + 1 < NK) {
+        wait_tiles<G::GPS, AHEAD>(min(NK - g - 2, AHEAD));
+        __builtin_amdgcn_s_barrier();
+      }
+    }
+  }
+
+  // epilogue: the shared path over the tile's row map. store_out adds
+  // blockIdx.z slabs, which is 0 on this 1-D grid: the chunk's slab is put
+  // into the pointer instead.
+  const ConvOut out{Bias, Y, SLAB ? Y32 + (long)z * M * Kp : nullptr, M, Kp,
+                    Klog, act};
+  TileRows<IMG7> rows;
+  rows.M = M;
+  rows.W = W;
+  if constexpr (IMG7)
+    rows.m00 = (long)tile * Map::ROWS;
+  else
+    rows.m00 = ((long)nImg * H + oy0) * W + ox0;
+  store_tile<SLAB, 16>(acc, rows, wr * FM * 16, n0 + wc * (FN * 16), lane,
+                       out);
+}
+
 // Split-K finalize: Y = act(sum over gz slabs of Y32 + bias), pad zeroed.
 // GZ is a template constant so all slab loads issue in parallel (the
 // runtime-bounded loop serialized up to 8 dependent ~500-cycle loads per
@@ -865,7 +1206,8 @@ enum ConvTier {
   TIER_IGEMM = 0,
   TIER_SPLITK = 1,
   TIER_IGEMM8 = 2,
-  TIER_PATCH = 3
+  TIER_PATCH = 3,
+  TIER_TILE = 4
 };
 
 struct ConvPlan {
@@ -873,7 +1215,8 @@ struct ConvPlan {
   int BN;      // N tile: 16 / 32 / 64 / 128
   int gx, gy;  // 128-row M blocks, BN-wide N blocks
   int nk;      // 32-wide K tiles
-  int gz;      // split-K slices (1 unless tier == TIER_SPLITK)
+  int gz;      // split-K slices (TIER_SPLITK) or channel chunks (TIER_TILE)
+  int cc;      // TIER_TILE: channels per chunk; gx = its tiles
 };
 
 // k_conv_patch is instantiated for KS 3/5/7 with Cp and Kp each 64 or 128.
@@ -902,9 +1245,62 @@ inline int conv_patch_knob() {
   return knob;
 }
 
+// k_conv_tile: k3, Cp 128 / 256 / 512 in 64- or 128-channel chunks, Kp a
+// multiple of its 128-wide N tile, whole 14x14 tiles or 7x7 images.
+inline bool conv_tile_eligible(int H, int W, int Cp, int Kp, int ks) {
+  return ks == 3 && (Cp == 128 || Cp == 256 || Cp == 512) && Kp % 128 == 0 &&
+         ((H % 14 == 0 && W % 14 == 0) || (H == 7 && W == 7));
+}
+inline int conv_tile_tiles(int N, int H, int W) {
+  return H == 7 ? (N + 3) / 4 : N * (H / 14) * (W / 14);
+}
+
+// WN_CONV_TILE as WN_CONV_PATCH, read once per process: 0 disables the tile
+// tier, 1 forces it wherever it is eligible, unset (-1) follows
+// conv_tile_wins. WN_CONV_TILE_CC (64 / 128) is a bench-only knob: it
+// overrides the chunk width of a shape that runs the tier, for the per-shape
+// A/B (tools/conv_tile_ab.py) and the tests of both widths.
+inline int conv_tile_on() {
+  static const int knob = [] {
+    const char* e = getenv("WN_CONV_TILE");
+    return e ? (atoi(e) != 0 ? 1 : 0) : -1;
+  }();
+  return knob;
+}
+inline int conv_tile_cc_knob() {
+  static const int cc = [] {
+    const char* e = getenv("WN_CONV_TILE_CC");
+    const int k = e ? atoi(e) : 0;
+    return k == 64 || k == 128 ? k : 0;
+  }();
+  return cc;
+}
+
+// Chunk width the tile tier runs a shape at by default, 0 where the shape
+// stays on its present tier. One row per class measured in the per-shape A/B
+// (docs/KERNELS.md, k_conv_tile table; profiles/r12_conv_tile_ab.jsonl): a
+// class is listed, at its faster width, only if every tile repeat beat the
+// fastest repeat of its present tier. Measured at N = 16 (the flagship
+// batch); smaller batches and every other size were not measured and stay
+// where they are. Not listed because it lost: 7^2 512->512 (both widths).
+struct ConvTileWin { int hw, Cp, Kp, cc; };
+constexpr ConvTileWin CONV_TILE_WINS[] = {
+    {56, 128, 128, 128},  // igemm8
+    {28, 128, 256, 128}, {28, 256, 128, 64}, {28, 256, 256, 128},
+    {14, 256, 512, 64},  {14, 512, 256, 64}, {14, 512, 512, 128},
+};
+constexpr int CONV_TILE_MIN_N = 16;
+inline int conv_tile_wins(int N, int H, int W, int Cp, int Kp) {
+  if (N < CONV_TILE_MIN_N || H != W) return 0;
+  for (const ConvTileWin& w : CONV_TILE_WINS)
+    if (w.hw == H && w.Cp == Cp && w.Kp == Kp) return w.cc;
+  return 0;
+}
+
 inline ConvPlan conv_plan(int N, int H, int W, int Cp, int Kp, int ks) {
   const long M = (long)N * H * W;
   ConvPlan p;
+  p.cc = 0;
   p.BN = Kp >= 128 ? 128 : Kp == 64 ? 64 : Kp == 32 ? 32 : 16;
   p.gx = (int)((M + 127) / 128);
   p.gy = (Kp + p.BN - 1) / p.BN;
@@ -940,6 +1336,23 @@ inline ConvPlan conv_plan(int N, int H, int W, int Cp, int Kp, int ks) {
     const int knob = conv_patch_knob();
     if (knob == 1 || (knob == -1 && conv_patch_wins(ks, Cp, Kp)))
       p.tier = TIER_PATCH;
+  }
+  // The tile tier takes over from the split-K igemm and from igemm8 (never
+  // from the patch tier), by the knob or the measured table.
+  if ((p.tier == TIER_SPLITK || p.tier == TIER_IGEMM8) &&
+      conv_tile_eligible(H, W, Cp, Kp, ks)) {
+    const int knob = conv_tile_on();
+    int cc = knob == 0 ? 0 : conv_tile_wins(N, H, W, Cp, Kp);
+    if (knob == 1 && cc == 0) cc = 128;
+    if (cc != 0 && conv_tile_cc_knob() != 0) cc = conv_tile_cc_knob();
+    if (cc != 0) {
+      p.tier = TIER_TILE;
+      p.BN = 128;
+      p.cc = cc;
+      p.gx = conv_tile_tiles(N, H, W);
+      p.gy = Kp / 128;
+      p.gz = Cp / cc;
+    }
   }
   return p;
 }
@@ -984,6 +1397,44 @@ void launch_conv_bn(const at::Tensor& x, const at::Tensor& wp,
   };
   dispatch_int_or<16, 128, 64, 32, 16>(plan.BN, [&](auto bn_const) {
     constexpr int BN = decltype(bn_const)::value;
+    if constexpr (BN == 128 && KS == 3) {
+      if (plan.tier == TIER_TILE) {  // deep k3 layers: tile-resident
+        const bool slab = gz > 1;
+        at::Tensor y32;
+        if (slab)
+          y32 = at::empty({gz, M, (long)Kp}, x.options().dtype(at::kFloat));
+        float* y32p = slab ? y32.data_ptr<float>() : nullptr;
+        const dim3 grid(plan.gx * gy * gz);
+        dispatch_int<64, 128>(plan.cc, "k_conv_tile CC", [&](auto cc_const) {
+          constexpr int CC = decltype(cc_const)::value;
+          dispatch_int<0, 1>(H == 7, "IMG7", [&](auto i7_const) {
+            constexpr bool I7 = decltype(i7_const)::value != 0;
+            using G = ConvTileGeo<CC, I7>;
+            dispatch_int<0, 1>(slab, "SLAB", [&](auto sl_const) {
+              constexpr bool SL = decltype(sl_const)::value != 0;
+              with_args([&](auto... a) {
+                hipLaunchKernelGGL((k_conv_tile<CC, I7, SL>), grid,
+                                   dim3(G::THREADS), (size_t)G::LDS_BYTES,
+                                   stream, a..., y32p, plan.gx);
+              });
+            });
+          });
+        });
+        if (slab) {
+          const long total = M * Kp;
+          const int fb = (int)std::min<long>(512, (total / 4 + 255) / 256);
+          dispatch_int<2, 4, 8>(gz, "k_conv_tile gz", [&](auto gz_const) {
+            constexpr int GZ = decltype(gz_const)::value;
+            hipLaunchKernelGGL((k_splitk_finalize<GZ>), dim3(fb), dim3(256),
+                               0, stream, y32p, bptr, (bf16_t*)y.data_ptr(),
+                               M, Kp, Klog, act);
+          });
+        }
+        return;
+      }
+    }
+    TORCH_CHECK(plan.tier != TIER_TILE, "k_conv_tile<", KS, ", ", BN,
+                "> is not instantiated");
     if (plan.tier == TIER_SPLITK) {
       using G = IgemmGeo<BN, true>;
       auto y32 = at::empty({gz, M, (long)Kp}, x.options().dtype(at::kFloat));
@@ -1064,6 +1515,7 @@ std::tuple<std::string, int64_t, int64_t> conv2d_fwd_plan(
   const char* name = p.tier == TIER_SPLITK   ? "splitk"
                      : p.tier == TIER_IGEMM8 ? "igemm8"
                      : p.tier == TIER_PATCH  ? "patch"
+                     : p.tier == TIER_TILE   ? "tile"
                                              : "igemm";
   return {name, p.BN, p.gz};
 }
